@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: image-tokens/s fwd+bwd, ViT patch=2 at 512^2 (L = 65 536), 1..8 MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...               (the driver's N > 1 launch; RCCL DDP)
+
+A plain run does only what the headline figure needs: build the model, W untimed warm-up steps, exactly K timed
+steps, the optional output dump, one JSON line (`value` = tokens/s, `ms_per_step` = milliseconds per timed step).
+Everything else this file measures (listed under "`--full` also reports" below) takes steps or runs of its own and
+sits behind `--full`.
+
+`--dump-outputs DIR` writes what the timed path hands its caller in the last timed step (rank 0): `DIR/loss.npy`, the
+loss `TrainStep.step` / `GraphedStep.step` returns, float32, shape (1,). Model weights (torch.manual_seed(0)) and the
+batch (seed 1234 + rank) are the same from run to run, so two builds can be compared on it. Two runs of one build
+agree to ~3e-4 relative at the metric config, not to the bit: weight gradients summed with float atomics (the patch
+embedding's, csrc/patch_embed.hip) add in a different order from run to run and the later steps' weights carry that.
 
 `python bench.py --gpus N` with N > 1 outside torchrun starts the N ranks itself (torch.distributed.run as a child
 process, 127.0.0.1 rendezvous) before this process touches the GPU, and exits with its code; every rank checks
@@ -13,11 +24,12 @@ EncoderDecoderModel(ViT-small, p2, 512x512, 2-D) + ViTUNETR decoder, bf16 autoca
 backward (DDP gradient all-reduce over RCCL), Adam step — on synthetic U[0,1) images already on the GPU.
 Throughput = (world * B * L) tokens / step time (max over ranks).
 
-Also reported (rank 0): `roofline` of the dominant liblci kernel (HIP events on that kernel's launches in the
+`--full` also reports (rank 0): `roofline` of the dominant liblci kernel (HIP events on that kernel's launches in the
 last timed step; an untimed probe step picks it), per-kernel breakdown (two steps after the timed region), `cpu_baseline` = the CPU oracle's forward on a bounded sample (N = 1 only), and
 `secondary.swin_p2_128` = the same harness on BASELINE configs[2] (Swin-tiny + SwinUNETR, 128^3 patch 2, one
-volume per GPU), which north_star also names. `--workload` runs one of the other configs on its own.
-`--no-kernel-timer` drops the per-launch HIP events (for rocprofv3 PMC passes: the profiler serialises
+volume per GPU), which north_star also names; for the HIP-graph workloads, `config.eager_ms_per_step` (the same step
+timed eager). `--workload` runs one of the other configs on its own.
+With `--full`, `--no-kernel-timer` drops the per-launch HIP events (for rocprofv3 PMC passes: the profiler serialises
 dispatches and the extra event packets are not needed there); the line then has no `roofline`/`kernels`.
 """
 from __future__ import annotations
@@ -257,10 +269,20 @@ def timed_steps(step, steps, warmup, world, device, rank, label="", on_start=Non
 GRAPHED = ("swin_p2_128", "swin_mamba_p2_128", "swin_hyena_p2_128", "vit_p4_512")
 
 
+def write_dump(dump_dir, loss):
+    """--dump-outputs: what the timed step hands its caller, the loss tensor, as float32 `loss.npy` of shape (1,)."""
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, "loss.npy"), loss.detach().float().cpu().numpy().reshape(1))
+
+
 def run_workload(workload, batch, steps, warmup, rank, world, device, kernel_timer=True, cfg_extra=(),
-                 ckpt_blocks=None, use_graph=None):
+                 ckpt_blocks=None, use_graph=None, full=False, dump_dir=None):
     """Build the workload's model, run `warmup` untimed and `steps` timed training steps (barrier + sync on both
-    sides, max over ranks). Returns the bench dict on rank 0 (None elsewhere); frees the model."""
+    sides, max over ranks). Returns the bench dict on rank 0 (None elsewhere); frees the model. `full` adds the
+    per-kernel figures (probe step, events in the last timed step, two breakdown steps after the timed region, the
+    graphed workloads' eager re-timing); `dump_dir` stores the last timed step's loss (rank 0)."""
+    kernel_timer = kernel_timer and full
     if workload in ("swin_p2_128", "vit_mamba_p2_256", "swin_mamba_p2_128", "swin_hyena_p2_128"):
         # any 3-D conv left on MIOpen (none in these heads today): heuristic solver instead of a minutes-long find
         os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")
@@ -311,21 +333,25 @@ def run_workload(workload, batch, steps, warmup, rank, world, device, kernel_tim
     if graphed:
         elapsed, loss = timed_steps(gstep.step, steps, warmup, world, device, rank, label=workload)
         loss = loss.detach().clone()   # the replay's loss lives in the graph's memory pool, released below
+        if dump_dir is not None and rank == 0:
+            write_dump(dump_dir, loss)
         del gstep
         torch.cuda.synchronize(device)
-        # the same step eager (N > 1 runs are eager: DDP's all-reduce hooks are not captured), so a scaling ratio
-        # against this N = 1 line can compare like with like
-        e_el, _ = timed_steps(lambda: trainer.step(x, y), min(steps, 5), 1, world, device, rank)
-        eager_ms = round(1000.0 * e_el / min(steps, 5), 2)
-        kernels.KernelTimer.reset()
-        kernels.KernelTimer.enabled = kernel_timer
-        for _ in range(2):
-            # a ~0.1 s device-side spin first, so the host has queued the whole step before the GPU reaches it: the
-            # per-launch events then bracket kernel time only, not the GPU idling while the host enqueues (these
-            # steps are host-paced when eager; without it small kernels read 2-3x their rocprofv3 durations)
-            torch.cuda._sleep(250_000_000)
-            trainer.step(x, y)
-        nk = 2
+        nk = steps
+        if full:
+            # the same step eager (N > 1 runs are eager: DDP's all-reduce hooks are not captured), so a scaling ratio
+            # against this N = 1 line can compare like with like
+            e_el, _ = timed_steps(lambda: trainer.step(x, y), min(steps, 5), 1, world, device, rank)
+            eager_ms = round(1000.0 * e_el / min(steps, 5), 2)
+            kernels.KernelTimer.reset()
+            kernels.KernelTimer.enabled = kernel_timer
+            for _ in range(2):
+                # a ~0.1 s device-side spin first, so the host has queued the whole step before the GPU reaches it:
+                # the per-launch events then bracket kernel time only, not the GPU idling while the host enqueues
+                # (these steps are host-paced when eager; without it small kernels read 2-3x their rocprofv3 durations)
+                torch.cuda._sleep(250_000_000)
+                trainer.step(x, y)
+            nk = 2
     else:
         # One untimed probe step with every liblci launch timed picks the dominant kernel; inside the timed region
         # only that kernel's launches of the last step carry events (an event pair on each of the ~400 launches of
@@ -349,6 +375,8 @@ def run_workload(workload, batch, steps, warmup, rank, world, device, kernel_tim
                 kernels.KernelTimer.enabled = kernel_timer and i == steps - 1
         elapsed, loss = timed_steps(lambda: trainer.step(x, y), steps, warmup, world, device, rank,
                                     label=workload, on_start=on_timed_start, on_step=on_step)
+        if dump_dir is not None and rank == 0:
+            write_dump(dump_dir, loss)
         nk = steps
         if kernels.KernelTimer.only is not None:
             kernels.KernelTimer.enabled = False
@@ -434,9 +462,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default 2; 1 for the 3-D configs)")
     ap.add_argument("--workload", default="vit_p2_512", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report roofline, per-kernel breakdown, eager re-timing of the graphed workloads, the "
+                         "secondary Swin 128^3 line and the CPU baseline (extra steps and runs after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (the loss it returns; rank 0) as float32 DIR/loss.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the Swin 128^3 line that the default (ViT 512^2) run also reports")
+                    help="with --full: skip the Swin 128^3 line that the default (ViT 512^2) run also reports")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--ckpt-blocks", type=int, default=None,
                     help="checkpoint the first K encoder blocks (default: 10 of 12 for vit_mamba_p2_256, else none)")
@@ -472,13 +505,14 @@ def main():
         torch.cuda.set_device(device)
         tuned = use_tuned_gemms()
     res = run_workload(args.workload, args.batch, args.steps, args.warmup, rank, world, device,
-                       kernel_timer=not args.no_kernel_timer, ckpt_blocks=args.ckpt_blocks)
-    if args.workload == "vit_p2_512" and not args.no_secondary:
+                       kernel_timer=not args.no_kernel_timer, ckpt_blocks=args.ckpt_blocks, full=args.full,
+                       dump_dir=args.dump_outputs)
+    if args.full and args.workload == "vit_p2_512" and not args.no_secondary:
         # north_star also asks for tokens/s on 128^3 patch-2 volumes (BASELINE configs[2], Swin + SwinUNETR):
         # same DDP harness, 1 volume per GPU, same steps (at most 10), reported under "secondary"
         try:
             sec = run_workload("swin_p2_128", 1, min(args.steps, 10), 2, rank, world, device,
-                               kernel_timer=not args.no_kernel_timer)
+                               kernel_timer=not args.no_kernel_timer, full=True)
         except Exception as e:   # never lose the headline line to the secondary workload
             sec = {"error": f"{type(e).__name__}: {e}"}
         if rank == 0:
@@ -486,7 +520,7 @@ def main():
             res["secondary"] = {"swin_p2_128": {k: sec[k] for k in keep if k in sec} if "error" not in sec else sec}
     if rank == 0:
         res["config"]["tuned_gemms"] = tuned
-        if world == 1 and not args.no_cpu_baseline and args.workload == "vit_p2_512":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "vit_p2_512":
             res["cpu_baseline"] = cpu_baseline(args.cpu_budget)
         print(json.dumps(res), flush=True)
     if world > 1:

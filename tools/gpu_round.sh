@@ -17,7 +17,7 @@ for s in $STEPS; do
         -p no:cacheprovider > $OUT/gputest.log 2>&1
       rc=$?; tail -3 $OUT/gputest.log; [ $rc -le 1 ] || stop tests $rc ;;
     bench)
-      timeout -k 10 600 python -u $ROOT/bench.py > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 600 python -u $ROOT/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; cat $OUT/bench.json | cut -c1-400; [ $rc -eq 0 ] || stop bench $rc ;;
     trace)
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run \

@@ -18,7 +18,7 @@ for r in 1 2; do
   done
 done
 for v in 0 1 0 1; do
-  LCI_WGRAD_DMA=$v timeout -k 10 400 python $ROOT/bench.py --workload swin_p2_128 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c3_$v.json 2> $OUT/c3_$v.err \
+  LCI_WGRAD_DMA=$v timeout -k 10 400 python $ROOT/bench.py --full --workload swin_p2_128 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/c3_$v.json 2> $OUT/c3_$v.err \
     || { echo "STOP bench $v"; tail -3 $OUT/c3_$v.err; exit 1; }
   python3 -c "import json,sys; j=json.loads(open('$OUT/c3_$v.json').read().strip().splitlines()[-1]); print('C3 LCI_WGRAD_DMA=$v', j['ms_per_step'], j['kernels'].get('conv3_wgrad'))" | tee -a $OUT/c3_ab.txt
 done

@@ -24,7 +24,7 @@ for v in winold winnew; do
 done
 cd $ROOT
 for v in winold winnew winold winnew; do
-  LCI_LIB_PATH=$ROOT/build_variants/liblci_$v.so timeout -k 10 400 python $ROOT/bench.py --workload swin_p2_128 --steps 10 \
+  LCI_LIB_PATH=$ROOT/build_variants/liblci_$v.so timeout -k 10 400 python $ROOT/bench.py --full --workload swin_p2_128 --steps 10 \
     --warmup 3 --no-cpu-baseline > $OUT/c3_$v.json 2> $OUT/c3_$v.err || { echo "STOP bench $v"; tail -3 $OUT/c3_$v.err; exit 1; }
   python3 -c "import json; j=json.loads(open('$OUT/c3_$v.json').read().strip().splitlines()[-1]); k=j['kernels']; print('C3 $v', j['ms_per_step'], {n: k[n]['ms_per_step'] for n in k if 'win' in n})" | tee -a $OUT/c3_ab.txt
 done
