@@ -38,6 +38,8 @@
  *                         (backbone_vit.py:249, MONAI MLPBlock) and the weight / bias gradient of (SABlock qkv / out_proj
  *                         backbone_vit.py:166-167, MONAI MLPBlock linear1/2, MambaVisionMixer in/x/dt/out_proj
  *                         mamba.py:60-64,90, HyenaOperator in/out_proj hyena.py:278-279, Swin qkv/proj/mlp)
+ *   lci_enhance_loss      Combined_Loss(["mse", "charbonnier", "gaussian3D"], [1, 1, 1]) (loss/loss_base.py:28-29,
+ *                         loss/loss_functions/enhancement_losses.py:18-278) and its gradient
  */
 #ifndef LCI_H_
 #define LCI_H_
@@ -59,8 +61,8 @@ extern "C" {
  * lci_gemm_bt; 23: lci_fftconv_spectrum Dv; 24: lci_inorm_finalize; 25: lci_adam_step; 26: Hyena gate dx2 / gx2
  * in the activation dtype; 27: lci_layernorm_bwd dxb; 28: lci_resample_cl_fwd, lci_resample1d_adj_ac; 29: lci_bn_relu_*; 30: lci_gemm_bt_acc;
  * 31: lci_layernorm_bwd dres2; 32: one-chunk selective scan without end-state workspaces (xend / xinit / sdt null),
- * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc). */
-#define LCI_ABI_VERSION 33
+ * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes). */
+#define LCI_ABI_VERSION 34
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -461,6 +463,25 @@ int lci_adam_max_tensors(void);
 int lci_adam_step(float* const* p, const float* const* g, float* const* m, float* const* v, const float* const* step,
                   const long long* n, int nt, double lr, double beta1, double beta2, double weight_decay, double eps,
                   int adamw, int maximize, void* stream);
+
+/* ------------------------------------------------------------------ CombinationEnhance loss (csrc/loss.hip)
+ * The enhancement recipes' loss (--loss_func=CombinationEnhance: mse + charbonnier + gaussian3D, weights 1, no
+ * per-sample weights, complex_i off) and its gradient in one call, for one-channel volumes: outputs, targets
+ * (B, 1, T, H, W) contiguous, each f32 or bf16 (dtype codes above). With d = outputs - targets, N = B T H W and
+ * g_k = the zero-padded 'same' correlation of d (per sample) with the separable stencil k = 0..2:
+ *   result[4] f32 = {loss, mse, charbonnier, gaussian3D} = {sum of the three, mean d^2, mean sqrt(d^2 + 1e-6),
+ *                    (1/3) sum_k mean |g_k|};
+ *   grad (outputs' shape and dtype) = d loss / d outputs = (2 d + d / sqrt(d^2 + 1e-6)
+ *                    + (1/3) sum_k transposed-stencil_k(sign g_k)) / N, sign(0) = 0. f32 arithmetic throughout.
+ * taps: (3, 3, 7) f32 in device memory: for stencil k the 1-D factors along T, H, W, centred at index 3 and zero past
+ *   the factor's half-width (at most 2 along T, 3 along H and W); stencil k = outer product of its three factors.
+ * ws: lci_enhance_loss_ws_bytes(B, T, H, W) bytes, 16-byte aligned, written and read by the call (per-workgroup
+ *   partial sums, then one byte of packed signs per voxel). T, H or W of 1 runs the pointwise terms only (odd
+ *   antisymmetric factors have a zero centre tap, so the stencil term is 0): gaussian3D is exactly 0 and ws holds
+ *   no sign map. No atomics (bitwise reproducible), no host sync; a NaN in the inputs propagates to the loss. */
+long long lci_enhance_loss_ws_bytes(int B, int T, int H, int W);
+int lci_enhance_loss(const void* outputs, int out_dtype, const void* targets, int tgt_dtype, const float* taps,
+                     void* grad, float* result, void* ws, int B, int T, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }

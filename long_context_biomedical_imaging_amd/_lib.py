@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "liblci.so")
 LIB_PATH = os.environ.get("LCI_LIB_PATH", DEFAULT_LIB)   # override: kernel-variant A/B runs (no staleness check)
-ABI_VERSION = 33   # include/lci.h LCI_ABI_VERSION
+ABI_VERSION = 34   # include/lci.h LCI_ABI_VERSION
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -90,6 +90,7 @@ SIGNATURES = {
     "lci_hyena_filter_fwd": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
     "lci_adam_step": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _I, _P],
     "lci_hyena_filter_bwd": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "lci_enhance_loss": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
 }
 
 _lib = None
@@ -164,6 +165,8 @@ def load(path: str = LIB_PATH):
     lib.lci_direct_conv_max_len.argtypes = []
     lib.lci_direct_conv_dk_splits.restype = ctypes.c_int
     lib.lci_direct_conv_dk_splits.argtypes = [_I, _I, _I]
+    lib.lci_enhance_loss_ws_bytes.restype = ctypes.c_longlong
+    lib.lci_enhance_loss_ws_bytes.argtypes = [_I, _I, _I, _I]
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argt

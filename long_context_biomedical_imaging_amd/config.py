@@ -49,7 +49,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--encoder_name", type=str, default="ViT", choices=["ViT", "Swin", "Identity"])
     p.add_argument("--decoder_name", type=str, default="ViTUNETR")
     p.add_argument("--task_type", type=str, default="seg", choices=["class", "seg", "enhance"])
-    p.add_argument("--loss_func", type=str, default="CrossEntropy", choices=["CrossEntropy", "MSE"])
+    p.add_argument("--loss_func", type=str, default="CrossEntropy", choices=["CrossEntropy", "MSE", "CombinationEnhance"])
     p.add_argument("--height", type=int, default=512)
     p.add_argument("--width", type=int, default=512)
     p.add_argument("--time", type=int, default=1)

@@ -2272,3 +2272,58 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1: flo
         _lib.call("lci_adam_step", arr(params[sl]), arr(grads[sl]), arr(exp_avgs[sl]), arr(exp_avg_sqs[sl]),
                   arr(steps[sl]), sizes, n, float(lr), float(beta1), float(beta2), float(weight_decay), float(eps),
                   int(decoupled), int(maximize), st)
+
+
+# ------------------------------------------------------------------------------------------- enhancement loss
+class _EnhanceLoss(torch.autograd.Function):
+    """lci_enhance_loss: the loss, its components and d loss / d outputs in one call on the current stream (no host
+    sync, no atomics). The gradient is kept for the backward, which only scales it by the upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, outputs, targets, taps):
+        B, _, T, H, W = outputs.shape
+        lib = _lib.load()
+        ws = torch.empty(max(16, lib.lci_enhance_loss_ws_bytes(B, T, H, W)), device=outputs.device, dtype=torch.uint8)
+        grad = torch.empty_like(outputs)
+        res = torch.empty(4, device=outputs.device, dtype=torch.float32)
+        code = {torch.float32: 0, torch.bfloat16: 1}
+        elems = outputs.numel()
+        traffic = float(elems * (2 * outputs.element_size() + targets.element_size()))
+        KernelTimer.run("enhance_loss", traffic, outputs, lambda: _lib.call(
+            "lci_enhance_loss", outputs.data_ptr(), code[outputs.dtype], targets.data_ptr(), code[targets.dtype],
+            taps.data_ptr(), grad.data_ptr(), res.data_ptr(), ws.data_ptr(), B, T, H, W, _lib.stream_of(outputs)))
+        ctx.save_for_backward(grad)
+        loss, comps = res[0], res[1:]
+        ctx.mark_non_differentiable(comps)
+        return loss, comps
+
+    @staticmethod
+    def backward(ctx, dloss, _dcomps):
+        (grad,) = ctx.saved_tensors
+        return (grad * dloss).to(grad.dtype), None, None
+
+
+def enhance_loss(outputs: torch.Tensor, targets: torch.Tensor, taps: torch.Tensor | None = None):
+    """The reference's CombinationEnhance loss (mse + charbonnier + gaussian3D, loss/loss_base.py:28-29) of one-channel
+    (B, 1, T, H, W) f32 / bf16 CUDA tensors on csrc/loss.hip. Returns (loss, components): the f32 scalar loss, which
+    back-propagates to `outputs`, and the detached (mse, charbonnier, gaussian3D) f32 tensor. taps: the (3, 3, 7) f32
+    stencil-factor table (losses.enhance_taps; the reference's sigmas when None)."""
+    if outputs.dim() != 5 or outputs.shape != targets.shape:
+        raise ValueError(f"enhance_loss: outputs {tuple(outputs.shape)} and targets {tuple(targets.shape)} must be "
+                         "the same (B, C, T, H, W) shape")
+    if outputs.shape[1] != 1:
+        raise ValueError(f"enhance_loss: C = {outputs.shape[1]}; the reference's gaussian3D term runs conv3d with "
+                         "groups=C on a one-channel weight, which only works for C == 1")
+    if taps is None:
+        from . import losses
+        taps = losses.enhance_taps(outputs.device)
+    outputs, targets = outputs.contiguous(), targets.detach().contiguous()
+    _lib.require_gpu(outputs, targets, taps)
+    for t in (outputs, targets):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.LciError(f"enhance_loss: dtype {t.dtype} (f32 or bf16 only)")
+    if taps.dtype != torch.float32 or tuple(taps.shape) != (3, 3, 7):
+        raise _lib.LciError("enhance_loss: taps must be a (3, 3, 7) f32 table")
+    if outputs.numel() == 0:
+        raise _lib.LciError("enhance_loss: empty tensors")
+    return _EnhanceLoss.apply(outputs, targets, taps)

@@ -148,6 +148,9 @@ def build_optimizer(params, config):
 def loss_fn(config):
     if config.loss_func == "CrossEntropy":
         return nn.CrossEntropyLoss()
+    if config.loss_func == "CombinationEnhance":   # loss/loss_base.py:28-29, the enhancement recipes' loss
+        from .losses import CombinationEnhanceLoss
+        return CombinationEnhanceLoss()
     return nn.MSELoss()
 
 

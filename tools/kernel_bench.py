@@ -8,6 +8,8 @@ Prints one JSON line per kernel with the algorithmic work per launch and the roo
               bytes/token fwd 2*(3*192+16)=1184, bwd 1984
   fftconv     ViT-hyena 512^2 p2: rows B*D = 768, L = 65536, f32 in/out: bytes/row-elem 8 fwd, 16 bwd
   patch embed ViT p2 512^2: image 4 B/px + tokens B*L*384*4 B
+  loss        CombinationEnhance fwd+bwd, fused op vs the torch composite, at the run_cmr / run_micro / C3 shapes:
+              minimal traffic = read outputs and targets, write the gradient (12 B/voxel f32, 8 with bf16 outputs)
 """
 import json
 import os
@@ -336,6 +338,65 @@ def bench_gemm_swin():
              f"M{M} K{K} N{N} bf16 (hipBLASLt)")
 
 
+def bench_loss():
+    """CombinationEnhance loss, forward + backward: the fused op (kernels.enhance_loss, csrc/loss.hip) against the
+    reference's formula through torch (tests/test_enhance_loss_cpu.formula with the fixture's windows: six elementwise
+    terms and three conv3d per step) in f32 and under bf16 autocast, at the shapes of run_cmr.sh, run_micro.sh and C3.
+    Per path: time, peak memory above the resident inputs, and for the fused op its minimal traffic (read outputs and
+    targets once, write the gradient once) over time as a share of the HBM peak."""
+    os.environ.setdefault("MIOPEN_FIND_MODE", "FAST")   # the composite's conv3d: heuristic solver, no minutes-long find
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from test_enhance_loss_cpu import formula, golden_windows
+    windows = [w.cuda() for w in golden_windows(torch.float32)]
+
+    def peak_of(fn, o):
+        o.grad = None                      # the previous run's gradient is not part of this run's footprint
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+    for shape, nm in (((16, 1, 32, 128, 128), "run_cmr"), ((4, 1, 1, 1024, 1024), "run_micro"),
+                      ((2, 1, 128, 128, 128), "C3")):
+        for odt, amp in ((torch.float32, False), (torch.bfloat16, True)):
+            o = torch.randn(*shape, device="cuda").to(odt).requires_grad_(True)
+            t = torch.randn(*shape, device="cuda")
+
+            def fused():
+                o.grad = None
+                loss, _ = kernels.enhance_loss(o, t)
+                loss.backward()
+
+            def composite():
+                o.grad = None
+                with torch.autocast(device_type="cuda", dtype=torch.bfloat16, enabled=amp):
+                    loss, _, _ = formula(o, t, windows)
+                loss.backward()
+
+            cfg = f"{nm} {shape} outputs {str(odt).replace('torch.', '')}" + (" autocast" if amp else "")
+            traffic = o.numel() * (2.0 * o.element_size() + t.element_size())
+            ms_f, ms_c = timeit(fused, iters=20), timeit(composite, iters=5)
+            ms_f2 = timeit(fused, iters=20)       # again after the composite: the spread of the fused figure
+            emit("enhance_loss fused fwd+bwd", min(ms_f, ms_f2), traffic, "GB/s", cfg)
+            print(json.dumps({"kernel": "enhance_loss torch composite fwd+bwd", "ms": round(ms_c, 3), "config": cfg,
+                              "fused_ms": [round(ms_f, 3), round(ms_f2, 3)],
+                              "speedup": round(ms_c / max(ms_f, ms_f2), 1),
+                              "peak_mib_fused": round(peak_of(fused, o), 1),
+                              "peak_mib_composite": round(peak_of(composite, o), 1)}), flush=True)
+            kernels.KernelTimer.reset()
+            kernels.KernelTimer.enabled = True
+            for _ in range(5):
+                fused()
+            kernels.KernelTimer.enabled = False
+            d = kernels.KernelTimer.summary()["enhance_loss"]
+            emit("enhance_loss launches only (no autograd, no upstream-gradient multiply)", d["avg_ms"], traffic, "GB/s",
+                 cfg)
+            del o, t
+            torch.cuda.empty_cache()
+
+
 def main():
     which = sys.argv[1:] or ["attention", "window", "scan", "fftconv", "patch", "linear", "mlp"]
     if "attention" in which:
@@ -367,6 +428,8 @@ def main():
         bench_gemm()
     if "gemm_swin" in which:
         bench_gemm_swin()
+    if "loss" in which:
+        bench_loss()
 
 
 if __name__ == "__main__":
