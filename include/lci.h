@@ -61,8 +61,9 @@ extern "C" {
  * lci_gemm_bt; 23: lci_fftconv_spectrum Dv; 24: lci_inorm_finalize; 25: lci_adam_step; 26: Hyena gate dx2 / gx2
  * in the activation dtype; 27: lci_layernorm_bwd dxb; 28: lci_resample_cl_fwd, lci_resample1d_adj_ac; 29: lci_bn_relu_*; 30: lci_gemm_bt_acc;
  * 31: lci_layernorm_bwd dres2; 32: one-chunk selective scan without end-state workspaces (xend / xinit / sdt null),
- * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes). */
-#define LCI_ABI_VERSION 34
+ * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes);
+ * 35: lci_attn_fwd_variant, lci_attn_fwd_pick. */
+#define LCI_ABI_VERSION 35
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -80,6 +81,16 @@ const char* lci_build_hash(void);
 int lci_attn_fwd(const void* qkv, void* out, float* lse2, float* knorm_ws, int B, int L, int H, int head_dim,
                  float scale, void* stream);
 long long lci_attn_fwd_ws_bytes(int B, int L, int H);
+/* lci_attn_fwd with the forward kernel forced, for tests and A/B timing: variant 0 = 64 queries per wave
+ * (attn_fwd_hs_kernel), 1 = 128 queries per wave (attn_fwd_hs4_kernel), -1 = what lci_attn_fwd does: the choice of
+ * lci_attn_fwd_pick for the current device's compute-unit count. Both kernels give bitwise the same out / lse2
+ * wherever they take the same (safe or exact) softmax path. */
+int lci_attn_fwd_variant(int variant, const void* qkv, void* out, float* lse2, float* knorm_ws, int B, int L, int H,
+                         int head_dim, float scale, void* stream);
+/* The kernel lci_attn_fwd runs for a shape on a device of n_cu compute units (0 / 1 as above). Pure host
+ * arithmetic, no device needed: wide only where its grid of W = B H ceil(L / 512) workgroups has W >= n_cu and
+ * W / (ceil(W / n_cu) n_cu) >= 0.9. */
+int lci_attn_fwd_pick(int B, int L, int H, int n_cu);
 /* dqkv (B, L, 3*H*64) bf16 <- dQ, dK, dV in the packed layout; dout (B, L, H*64) bf16;
  * delta_ws: 16-byte aligned workspace of lci_attn_bwd_ws_bytes(B, H, L) bytes, written by the call: the (B, H, 2, L)
  * f32 rows -lse2 | -delta (the backward kernels' row constants). No atomics: bitwise reproducible. */

@@ -9,7 +9,10 @@
 // stream of v_mfma_f32_32x32x16_bf16 and softmax VALU (inline asm, fixed order):
 // Forward:   attn_key_norm_kernel (per-64-key-tile max ||k||) + attn_fwd_hs_kernel: 64 queries per wave on the MFMA
 //            lane, S^T = K.Q~^T, lane-local max-free softmax on tiles the key-norm bound proves safe (exact online
-//            softmax otherwise), O^T += V^T.P^T with P straight from the S accumulators.
+//            softmax otherwise), O^T += V^T.P^T with P straight from the S accumulators. Where the grid still fills
+//            the chip (lci_attn_fwd_pick: the metric shape, L = 65536) attn_fwd_hs4_kernel runs instead: the same
+//            stream with 128 queries per wave, half the K | V staging, LDS reads and barriers per MFMA, bitwise the
+//            same O and lse2.
 // Backward:  (1) attn_bwd_delta_kernel: delta = rowsum(dO*O), written with -lse2 as the chains' row constants;
 //            (2) attn_bwd_dkdv_hs_kernel: 64 keys per wave on the lane, sweeps query tiles: S, dP recomputed,
 //            dV^T += dO^T.P, dK^T += Q^T.dS; (3) attn_bwd_dq_hs_kernel: 64 queries per wave, sweeps key tiles:
@@ -19,6 +22,7 @@
 #include "common.hpp"
 
 #include <type_traits>
+#include <utility>
 
 namespace lci {
 
@@ -1465,6 +1469,589 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
   }
 }
 
+// ------------------------------------------------ forward, wide: 128 queries per wave (four query blocks)
+// attn_fwd_hs_kernel's stream with FW4_NQB = 4 query blocks of 32 per wave, 512 queries per workgroup: every K | V
+// tile a workgroup stages (4 buffer loads + 4 ds_write_b128 per wave, one barrier, one staging wait) and every
+// fragment a wave reads from LDS (4 K rows, 8 V^T halves per 32-key half) now feeds 32 large MFMAs instead of 16, so
+// L2 -> LDS bytes, LDS instructions and synchronisation per MFMA are halved; the arithmetic per query is unchanged, in
+// the same order (m, the chain's k-steps, the bf16 packs, the key order into O^T, the per-half row-sum MFMAs and f32
+// adds), so O and lse2 are bitwise those of attn_fwd_hs_kernel wherever both take the same safe / unsafe path.
+// Per half (40 gaps), block b = 0..3: gaps 10b .. 10b+3 the S^T chain of block b, 10b+4, +5, +7, +8 O^T += V^T P^T of
+// block b-1 (block 3: of the previous half), 10b+6 / 10b+9 its row sums; the VALU of a block (FW4_SCHED_R,
+// tools/gen_fwd_sched.py --nqb 4) is the two-block placement shifted by 10 gaps per block, so at most two blocks' S
+// are live at a time. The row-sum adds of blocks 0 / 1 fall into the same half (gaps 22 / 23, 32 / 33), those of
+// blocks 2 / 3 into the next (2 / 3, 12 / 13). The next half's K rows are read at gaps 33-36 (each fragment 3 gaps
+// after the last chain's read of it). AGPRs: O^T 128, Q~ 64, selector 4, staging 16.
+constexpr int FW4_NQB = 4;                 // query blocks of 32 per wave
+constexpr int FW4_NG = 10 * FW4_NQB;       // gaps per half
+constexpr int FW4_QWG = HS_NW * 32 * FW4_NQB;   // queries per workgroup
+// gap  0 S0: E3.6 E3.7
+// gap  1 S0: E3.8 E3.9 C3.3
+// gap  2 S0: E3.10 E3.11 C3.4 A2.0
+// gap  3 S0: E3.12 E3.13 C3.5 A2.1
+// gap  4 P3: E3.14 E3.15 C3.6
+// gap  5 P3: C3.7 E0.0 E0.1
+// gap  6 R3: C0.0
+// gap  7 P3: E0.2 E0.3
+// gap  8 P3: E0.4 E0.5 C0.1
+// gap  9 R3: C0.2
+// gap 10 S1: E0.6 E0.7
+// gap 11 S1: E0.8 E0.9 C0.3
+// gap 12 S1: E0.10 E0.11 C0.4 A3.0
+// gap 13 S1: E0.12 E0.13 C0.5 A3.1
+// gap 14 P0: E0.14 E0.15 C0.6
+// gap 15 P0: C0.7 E1.0 E1.1
+// gap 16 R0: C1.0
+// gap 17 P0: E1.2 E1.3
+// gap 18 P0: E1.4 E1.5 C1.1
+// gap 19 R0: C1.2
+// gap 20 S2: E1.6 E1.7
+// gap 21 S2: E1.8 E1.9 C1.3
+// gap 22 S2: E1.10 E1.11 C1.4 A0.0
+// gap 23 S2: E1.12 E1.13 C1.5 A0.1
+// gap 24 P1: E1.14 E1.15 C1.6
+// gap 25 P1: C1.7 E2.0 E2.1
+// gap 26 R1: C2.0
+// gap 27 P1: E2.2 E2.3
+// gap 28 P1: E2.4 E2.5 C2.1
+// gap 29 R1: C2.2
+// gap 30 S3: E2.6 E2.7
+// gap 31 S3: E2.8 E2.9 C2.3
+// gap 32 S3: E2.10 E2.11 C2.4 A1.0
+// gap 33 S3: E2.12 E2.13 C2.5 A1.1
+// gap 34 P2: E2.14 E2.15 C2.6
+// gap 35 P2: C2.7 E3.0 E3.1
+// gap 36 R2: C3.0
+// gap 37 P2: E3.2 E3.3
+// gap 38 P2: E3.4 E3.5 C3.1
+// gap 39 R2: C3.2
+constexpr unsigned char FW4_SCHED_R[40][4] = {
+    {0x36, 0x37, 0xff, 0xff},
+    {0x38, 0x39, 0xb3, 0xff},
+    {0x3a, 0x3b, 0xb4, 0x60},
+    {0x3c, 0x3d, 0xb5, 0x61},
+    {0x3e, 0x3f, 0xb6, 0xff},
+    {0xb7, 0x00, 0x01, 0xff},
+    {0x80, 0xff, 0xff, 0xff},
+    {0x02, 0x03, 0xff, 0xff},
+    {0x04, 0x05, 0x81, 0xff},
+    {0x82, 0xff, 0xff, 0xff},
+    {0x06, 0x07, 0xff, 0xff},
+    {0x08, 0x09, 0x83, 0xff},
+    {0x0a, 0x0b, 0x84, 0x70},
+    {0x0c, 0x0d, 0x85, 0x71},
+    {0x0e, 0x0f, 0x86, 0xff},
+    {0x87, 0x10, 0x11, 0xff},
+    {0x90, 0xff, 0xff, 0xff},
+    {0x12, 0x13, 0xff, 0xff},
+    {0x14, 0x15, 0x91, 0xff},
+    {0x92, 0xff, 0xff, 0xff},
+    {0x16, 0x17, 0xff, 0xff},
+    {0x18, 0x19, 0x93, 0xff},
+    {0x1a, 0x1b, 0x94, 0x40},
+    {0x1c, 0x1d, 0x95, 0x41},
+    {0x1e, 0x1f, 0x96, 0xff},
+    {0x97, 0x20, 0x21, 0xff},
+    {0xa0, 0xff, 0xff, 0xff},
+    {0x22, 0x23, 0xff, 0xff},
+    {0x24, 0x25, 0xa1, 0xff},
+    {0xa2, 0xff, 0xff, 0xff},
+    {0x26, 0x27, 0xff, 0xff},
+    {0x28, 0x29, 0xa3, 0xff},
+    {0x2a, 0x2b, 0xa4, 0x50},
+    {0x2c, 0x2d, 0xa5, 0x51},
+    {0x2e, 0x2f, 0xa6, 0xff},
+    {0xa7, 0x30, 0x31, 0xff},
+    {0xb0, 0xff, 0xff, 0xff},
+    {0x32, 0x33, 0xff, 0xff},
+    {0x34, 0x35, 0xb1, 0xff},
+    {0xb2, 0xff, 0xff, 0xff}};
+static_assert(sizeof(FW4_SCHED_R) == FW4_NG * 4, "one row per gap");
+__host__ __device__ constexpr unsigned char fw4_sched(int g, int o) { return FW4_SCHED_R[g][o]; }
+// initial S^T of the last query block (its VALU wraps into the next half), as fw_wrapped_exp
+__host__ __device__ constexpr bool fw4_wrapped_exp(int i) {
+  for (int g = 0; g < 10 * (FW4_NQB - 1) + 5; ++g)
+    for (int o = 0; o < 4; ++o)
+      if (fw4_sched(g, o) == (((FW4_NQB - 1) << 4) | i)) return true;
+  return false;
+}
+// a block's row-sum adds run in the half after its row-sum MFMAs (true) or in the same half (false)
+__host__ __device__ constexpr bool fw4_add_wraps(int qb) { return 10 * qb + 22 >= FW4_NG; }
+
+template <class F, int... G>
+__device__ __forceinline__ void hs_for_gaps(F&& f, std::integer_sequence<int, G...>) {
+  (f(std::integral_constant<int, G>{}), ...);
+}
+
+__global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a, const float* knorm) {
+  constexpr int NQB = FW4_NQB;
+  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
+  constexpr int SLOT_B = 2 * TILE_B;                // K | V
+  constexpr int NSLOT = 4;
+  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
+  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ int unsafe_wg;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hh = blockIdx.y, b = blockIdx.z;
+  const int L = a.L;
+  const int h = lane >> 5, r32 = lane & 31;
+  const int qw0 = blockIdx.x * FW4_QWG + wave * (32 * NQB);
+  const int nkt = (L + KT - 1) / KT;
+  if (tid == 0) unsafe_wg = 0;
+
+  // the key-norm bound over the whole key range (first: the loop runs before the Q~ fragments take their registers)
+  const float* kn = knorm + ((long long)b * a.H + hh) * nkt;
+  float kmax = 0.f;
+  for (int t = lane; t < nkt; t += 64) kmax = fmaxf(kmax, kn[t]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) kmax = fmaxf(kmax, __shfl_xor(kmax, o));
+  HS_OPAQUE(kmax);
+  // Q~ = c q as B operands: lane holds q~[qw0 + 32 qb + r32][16 ks + 8h + j]; qn = ||q~|| of the lane's query
+  bf16x8 qf[NQB][4];
+  float qn[NQB];
+  auto load_q = [&](const bf16* qp, int qb, bf16x8 (&f)[4]) __attribute__((always_inline)) {   // returns sum q~^2
+    const int q = qw0 + 32 * qb + r32;
+    float ss = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      bf16x8 t{};
+      if (q < L) t = *(const bf16x8*)(qp + (long long)q * a.rs_q + 16 * ks + 8 * h);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        t[j] = to_bf16(to_f32(t[j]) * a.c);
+        ss += to_f32(t[j]) * to_f32(t[j]);
+      }
+      f[ks] = t;
+    }
+    return ss;
+  };
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) qn[qb] = sqrtf(wave_sum_xor32(load_q(a.q + b * a.bs_q + hh * a.hs, qb, qf[qb])));
+  // the exact row max of the first key tile
+  const bf16* kp = a.k + b * a.bs_k + hh * a.hs;
+  const bf16* vp = a.v + b * a.bs_v + hh * a.hs;
+  float m[NQB];
+  {
+    bf16x8 k0[2][4];
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int key = 32 * kb + r32;
+        k0[kb][ks] = key < L ? *(const bf16x8*)(kp + (long long)key * a.rs_k + 16 * ks + 8 * h) : bf16x8{};
+      }
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      float mx = NEG_BIG;
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        f32x16 sc = {};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) sc = mfma32(k0[kb][ks], qf[qb][ks], sc);
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (32 * kb + (i & 3) + 8 * (i >> 2) + 4 * h < L) mx = fmaxf(mx, sc[i]);
+      }
+      m[qb] = wave_max_xor32(mx);
+    }
+  }
+  __syncthreads();
+  {
+    bool safe = true;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) safe = safe && (qn[qb] * kmax - m[qb] <= SAFE_EXP2);
+    if (!__all(safe) && lane == 0) unsafe_wg = 1;
+  }
+  __syncthreads();
+  const int unsafe = __builtin_amdgcn_readfirstlane(unsafe_wg);
+
+  if (unsafe) {
+    // exact online softmax, 32 keys at a time (operands straight from global memory: the rare path), two query
+    // blocks per sweep over the keys: four blocks' O^T beside the compiler's own operand registers would not fit
+    auto sweep = [&](auto Q0) __attribute__((always_inline)) {
+    constexpr int q0 = decltype(Q0)::value;
+    // the sweep's own Q~ fragments, loaded again (through a pointer the compiler cannot match with the prologue's, so
+    // that the other pair's fragments do not stay live through this sweep)
+    const bf16* qp = a.q + b * a.bs_q + hh * a.hs;
+    asm volatile("" : "+s"(qp));
+    bf16x8 qf[NQB][4];
+#pragma unroll
+    for (int i = q0; i < q0 + 2; ++i) load_q(qp, i, qf[i]);
+    f32x16 o[NQB][2];
+    float mr[NQB], lr[NQB];
+#pragma unroll
+    for (int i = q0; i < q0 + 2; ++i) {
+      mr[i] = m[i];
+      lr[i] = 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) o[i][j] = f32x16{};
+    }
+    for (int k0 = 0; k0 < L; k0 += 32) {
+      bf16x8 kr[4], vt[2][2];
+      // rows past L read the last key's (no select, so no zero-initialised fragment registers): their scores are
+      // replaced by NEG_BIG below, and a score depends on its own key's row only
+      const int key = min(k0 + r32, L - 1);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) kr[ks] = *(const bf16x8*)(kp + (long long)key * a.rs_k + 16 * ks + 8 * h);
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {   // V^T: lane (h, d) holds V[key k(8h + j)][d], k-order of the P packs
+            const int kk = k0 + 16 * s2 + (j & 3) + 8 * (j >> 2) + 4 * h;
+            vt[db][s2][j] = kk < L ? vp[(long long)kk * a.rs_v + 32 * db + r32] : to_bf16(0.f);
+          }
+#pragma unroll
+      for (int qb = q0; qb < q0 + 2; ++qb) {
+        f32x16 sc = {};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) sc = mfma32(kr[ks], qf[qb][ks], sc);
+        float mx = NEG_BIG;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          if (k0 + (i & 3) + 8 * (i >> 2) + 4 * h >= L) sc[i] = NEG_BIG;
+          mx = fmaxf(mx, sc[i]);
+        }
+        const float mn = fmaxf(mr[qb], wave_max_xor32(mx));
+        const float alpha = exp2_fast(mr[qb] - mn);
+        mr[qb] = mn;
+        lr[qb] *= alpha;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { o[qb][0][i] *= alpha; o[qb][1][i] *= alpha; }
+        bf16x8 pk[2];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float p = exp2_fast(sc[i] - mn);
+          lr[qb] += p;
+          pk[i >> 3][i & 7] = to_bf16(p);
+        }
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+          for (int s2 = 0; s2 < 2; ++s2) o[qb][db] = mfma32(vt[db][s2], pk[s2], o[qb][db]);
+      }
+    }
+#pragma unroll
+    for (int qb = q0; qb < q0 + 2; ++qb) {
+      const int q = qw0 + 32 * qb + r32;
+      const float lt = wave_sum_xor32(lr[qb]);
+      if (q < L) {
+        const float inv = 1.f / lt;
+        bf16* op = a.out + b * a.bs_out + (long long)q * a.rs_out + hh * a.hs;
+#pragma unroll
+        for (int db = 0; db < 2; ++db)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            bf16x4 w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w[j] = to_bf16(o[qb][db][4 * g + j] * inv);
+            *(bf16x4*)(op + 32 * db + 8 * g + 4 * h) = w;
+          }
+        if (h == 0) a.lse2[((long long)b * a.H + hh) * L + q] = mr[qb] + __log2f(lt);
+      }
+    }
+    };
+    static_assert(NQB % 2 == 0, "the exact path sweeps the keys once per pair of query blocks");
+#pragma unroll
+    for (int q0 = 0; q0 < NQB; q0 += 2) {
+      if (q0 == 0) sweep(std::integral_constant<int, 0>{});
+      else sweep(std::integral_constant<int, 2>{});
+    }
+    return;
+  }
+
+  // ---- the placed stream
+#pragma unroll
+  for (int i = 0; i < NQB; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) HS_TO_AGPR(qf[i][j]);
+  const rsrc_t rk = make_rsrc(kp, (uint32_t)(L - 1) * (uint32_t)(a.rs_k * 2) + DH * 2);
+  const rsrc_t rv = make_rsrc(vp, (uint32_t)(L - 1) * (uint32_t)(a.rs_v * 2) + DH * 2);
+  const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
+  const int prow = lane >> 3;
+  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
+  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
+  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
+  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
+  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
+  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
+    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
+    if (i == 0) hs_dma16(rk, dk0, t * KT * rs2k, sb + 2048 * wave);
+    if (i == 1) hs_dma16(rk, dk1, t * KT * rs2k, sb + 2048 * wave + 1024);
+    if (i == 2) hs_dma16(rv, dv0, t * KT * rs2v, sb + TILE_B + 2048 * wave);
+    if (i == 3) hs_dma16(rv, dv1, t * KT * rs2v, sb + TILE_B + 2048 * wave + 1024);
+  };
+  // LDS byte offsets of every distinct fragment read within a ring slot (as attn_fwd_hs_kernel)
+  unsigned row_off[2][4], tr_off[2][4][2];   // [rows 0-31 | 32-63][k-step | fragment][part]
+#pragma unroll
+  for (int r0i = 0; r0i < 2; ++r0i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      row_off[r0i][k] = 2 * sw128(32 * r0i + r32, 16 * k + 8 * h);
+      HS_OPAQUE(row_off[r0i][k]);
+#pragma unroll
+      for (int part = 0; part < 2; ++part) {   // fragment k = (d block k & 1, k-step k >> 1)
+        const int rw = 32 * r0i + 16 * (k >> 1) + 4 * h + ((lane & 15) >> 2) + 8 * part;
+        const int col = 32 * (k & 1) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+        tr_off[r0i][k][part] = TILE_B + 2 * sw128(rw, col);
+        HS_OPAQUE(tr_off[r0i][k][part]);
+      }
+    }
+  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {
+    return *(const bf16x8*)(smem + row_off[r0i][ks] + soff);
+  };
+  auto trh = [&](int soff, int r0i, int f, int part) __attribute__((always_inline)) {
+    return lds_tr4((const bf16*)(smem + tr_off[r0i][f][part] + soff));
+  };
+
+  f32x16 o[NQB][2];   // [query block][d block] O^T, lane = query, rows d = 32 db + (i & 3) + 8 (i >> 2) + 4h
+  f32x16 S[NQB];      // [query block] S~^T - m, then P (rows = the half's 32 keys)
+  f32x16 NM[NQB];     // -m splat: the chains' initial accumulator
+  u32x4 pp[NQB][2];   // [query block][k-step] bf16 P^T packs
+  bf16x4 vt[2][2][2][2];   // [set][d block][k-step][half of the fragment] transposed V (keys as the k index)
+  bf16x8 kr[4];       // K row fragments (A operands of the chains)
+  float lp[NQB][2];   // [query block][row half] running f32 row sums (lanes 0-15: queries 16 s + lane)
+  f32x4 rs[NQB];      // [query block] the half's row-sum partial on the matrix pipe: D rows 0 / 1 in lanes 0-15
+  bf16x8 sel;         // 16x16x32 A operand: row 0 selects lane groups 0 / 2, row 1 groups 1 / 3 (all 8 k per lane)
+  {
+    const int m16 = lane & 15, g16 = lane >> 4;
+    const float one = (m16 == 0 && (g16 & 1) == 0) || (m16 == 1 && (g16 & 1) == 1) ? 1.f : 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sel[j] = to_bf16(one);
+    HS_TO_AGPR(sel);
+  }
+#pragma unroll
+  for (int i = 0; i < NQB; ++i) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) NM[i][e] = -m[i];
+    HS_OPAQUE(NM[i]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      o[i][j] = f32x16{};
+      HS_TO_AGPR(o[i][j]);
+      pp[i][j] = u32x4{};
+      HS_OPAQUE(pp[i][j]);
+    }
+    lp[i][0] = lp[i][1] = 0.f;
+    rs[i] = f32x4{};
+    HS_OPAQUE(rs[i]);
+  }
+  // only the last block's S is read (by its wrapped VALU) before a chain has written it
+#pragma unroll
+  for (int e = 0; e < 16; ++e) S[NQB - 1][e] = fw4_wrapped_exp(e) ? NEG_BIG : 0.f;
+  HS_OPAQUE(S[NQB - 1]);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        vt[0][i][j][k] = vt[1][i][j][k] = bf16x4{};
+        HS_OPAQUE(vt[0][i][j][k]);
+        HS_OPAQUE(vt[1][i][j][k]);
+      }
+
+  auto valu_op = [&](unsigned char cd, int only_qb) __attribute__((always_inline)) {
+    if (cd == 0xFF) return;
+    const int kind = cd >> 6, qb = (cd >> 4) & 3, i = cd & 15;
+    if (only_qb >= 0 && qb != only_qb) return;
+    if (kind == 0) HS_EXP(S[qb][i]);
+    else if (kind == 1) {
+      asm volatile("v_add_f32 %0, %0, %1" : "+v"(lp[qb][i]) : "v"(rs[qb][i]));
+      // rows 2 / 3 of the accumulator are never read, but the next MFMA writes all four registers: keep them
+      // allocated so that nothing else lives in them inside its hazard window
+      if (i == 1) HS_KEEP(rs[qb]);
+    } else HS_CVT(pp[qb][i >> 2][i & 3], S[qb][2 * i], S[qb][2 * i + 1]);
+  };
+  auto pv_mfma = [&](int k, int qb, int st) __attribute__((always_inline)) {   // k: (d block k & 1, k-step k >> 1)
+    const int db = k & 1, s2 = k >> 1;
+    HS_MFMA_G(o[qb][db], cat44(vt[st][db][s2][0], vt[st][db][s2][1]), __builtin_bit_cast(bf16x8, pp[qb][s2]));
+  };
+  // the half's row-sum partial of block qb: the column sums of its two P^T packs (k-step 0 starts from zero)
+  auto rs_mfma = [&](int qb, int s2) __attribute__((always_inline)) {
+    if (s2 == 0)
+      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(rs[qb]) : "a"(sel), "v"(pp[qb][0]));
+    else
+      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(rs[qb]) : "a"(sel), "v"(pp[qb][1]));
+  };
+  // gap g = 10 bq + r: r 0-3 the S chain of block bq | r 4 5 (6) 7 8 (9) PV / row sums of block bq - 1 (block 0's
+  // gaps: the last block, with the previous half's V^T set)
+  auto mfma_gap = [&](int g, int C, const f32x16 (&init)[NQB]) __attribute__((always_inline)) {
+    const int bq = g / 10, r = g % 10;
+    if (r < 4) {
+      if (r == 0) HS_MFMA_C0(S[bq], kr[0], qf[bq][0], init[bq]); else HS_MFMA_C(S[bq], kr[r], qf[bq][r]);
+    } else {
+      const int pq = (bq + NQB - 1) % NQB;
+      if (r == 6 || r == 9) rs_mfma(pq, r == 9);
+      else pv_mfma(r < 6 ? r - 4 : r - 5, pq, bq == 0 ? C ^ 1 : C);
+    }
+  };
+
+  // one 32-key half (rows 32 r0i of the slot at byte offset soff, V^T set SET): the transposed V fragments at gaps 0-7,
+  // the next half's K rows (rows 32 nr0i of the slot at nsoff) at gaps KR0 .. KR0+3, right behind the gap's MFMA
+  auto half = [&](auto SET, auto FIXED, int soff, int r0i, int nsoff, int nr0i, const f32x16 (&init)[NQB], auto hook)
+      __attribute__((always_inline)) {
+    constexpr int C = decltype(SET)::value;
+    constexpr bool FIXED_SLOT = decltype(FIXED)::value;
+    constexpr int NG = FW4_NG;
+    constexpr int KR0 = 10 * (NQB - 1) + 3;   // each fragment reloaded 3 gaps after the last chain's read of it
+    auto lds_reads = [&](int g) __attribute__((always_inline)) {
+      if (g < 8) {
+        const int f = g >> 1, part = g & 1;   // fragment f = (d block f & 1, k-step f >> 1)
+        vt[C][f & 1][f >> 1][part] = trh(soff, r0i, f, part);
+      } else if (g >= KR0 && g < KR0 + 4) {   // the next half's K rows
+        kr[g - KR0] = row(nsoff, nr0i, g - KR0);
+      }
+    };
+    // (unrolled by pack expansion: 40 gaps of this size are past the loop unroller's limit for `#pragma unroll`)
+    hs_for_gaps([&](auto G) __attribute__((always_inline)) {
+      constexpr int g = decltype(G)::value;
+      mfma_gap(g, C, init);
+      if (g % 10 == 2) HS_KEEP(init[g / 10]);   // the chain-start MFMAs read their initial accumulators as SrcC after issue
+      lds_reads(g);
+      // run-time-slot tiles (remainder, ragged last tile): the compiler may sink their LDS reads, so the wait states
+      // between a chain's last MFMA and its first exp are padded explicitly
+      if (!FIXED_SLOT && g % 10 == 5) asm volatile("s_nop 1" ::: "memory");
+      // a first-exp gap with no LDS read behind its MFMA: the wait state the read gives elsewhere
+      if (g % 10 == 5 && g >= 8 && !(g >= KR0 && g < KR0 + 4)) asm volatile("s_nop 0" ::: "memory");
+      valu_op(fw4_sched(g, 0), -1);
+      valu_op(fw4_sched(g, 1), -1);
+      valu_op(fw4_sched(g, 2), -1);
+      valu_op(fw4_sched(g, 3), -1);
+      hook(g);
+    }, std::make_integer_sequence<int, NG>{});
+  };
+
+  // register staging as attn_fwd_hs_kernel: tile t+1's pieces are stored to ring slot (t+1) & 3 at gaps 1-7 of tile
+  // t's half 0 and tile t+2's loaded at gaps 11-17; the barrier at gap 7 of tile t's half 1 publishes tile t+1 (first
+  // reader: the K rows at gaps KR0 ..)
+  u32x4 stg[4];
+  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
+    if (i == 0) stg[0] = hs_ld16(rk, dk0, t * KT * rs2k);
+    if (i == 1) stg[1] = hs_ld16(rk, dk1, t * KT * rs2k);
+    if (i == 2) stg[2] = hs_ld16(rv, dv0, t * KT * rs2v);
+    if (i == 3) stg[3] = hs_ld16(rv, dv1, t * KT * rs2v);
+  };
+  // prologue: tile 0 by LDS-DMA, tile 1 into the staging AGPRs; wait for tile 0; K rows of its first half
+  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
+  hs_vmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) kr[ks] = row(0, 0, ks);
+  __builtin_amdgcn_s_waitcnt(LGKM0_WAIT);
+
+  // SL >= 0: tile t sits in ring slot SL (compile-time: immediates); SL < 0: slot t & 3 at run time. ia / ib: the
+  // chains' initial accumulators of half 0 / 1; mid() runs between the halves
+  auto tile = [&](auto SL, int t, const f32x16 (&ia)[NQB], const f32x16 (&ib)[NQB], auto mid)
+      __attribute__((always_inline)) {
+    constexpr int sl = decltype(SL)::value;
+    const int soff = sl >= 0 ? sl * SLOT_B : (t & (NSLOT - 1)) * SLOT_B;
+    const int nsoff = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : ((t + 1) & (NSLOT - 1)) * SLOT_B;
+    auto stage = [&](int g) __attribute__((always_inline)) {
+      if (t + 1 < nkt && g == 7) __builtin_amdgcn_s_barrier();
+    };
+    constexpr int LD0 = 11;   // tile t+2's loads at gaps 11, 13, 15, 17 (32x32x16 gaps)
+    auto rstg = [&](int g) __attribute__((always_inline)) {
+      if (g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
+      if (g < 8 && (g & 1)) {
+        constexpr int S1 = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : 0;
+        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (NSLOT - 1)) * SLOT_B);
+        switch (g) {
+          case 1: hs_st16<S1>(base, stg[0]); break;
+          case 3: hs_st16<S1 + 1024>(base, stg[1]); break;
+          case 5: hs_st16<S1 + TILE_B>(base, stg[2]); break;
+          default: hs_st16<S1 + TILE_B + 1024>(base, stg[3]); break;
+        }
+      } else if (g >= LD0 && g < LD0 + 8 && ((g - LD0) & 1) == 0) {
+        ld_piece(t + 2, (g - LD0) >> 1);
+      }
+    };
+    half(std::integral_constant<int, 0>{}, std::bool_constant<(sl >= 0)>{}, soff, 0, soff, 1, ia, rstg);
+    mid();
+    half(std::integral_constant<int, 1>{}, std::bool_constant<(sl >= 0)>{}, soff, 1, nsoff, 0, ib, stage);
+  };
+  const bool ragged = (L & (KT - 1)) != 0;
+  const int nfast = ragged ? nkt - 1 : nkt;
+  using IC0 = std::integral_constant<int, 0>;
+  using IC1 = std::integral_constant<int, 1>;
+  using IC2 = std::integral_constant<int, 2>;
+  using IC3 = std::integral_constant<int, 3>;
+  using ICR = std::integral_constant<int, -1>;
+  auto nop = [] {};
+  int t = 0;
+  for (; t + 4 <= nfast; t += 4) {   // t & 3 == 0 here
+    tile(IC0{}, t, NM, NM, nop);
+    tile(IC1{}, t + 1, NM, NM, nop);
+    tile(IC2{}, t + 2, NM, NM, nop);
+    tile(IC3{}, t + 3, NM, NM, nop);
+  }
+  for (; t < nfast; ++t) tile(ICR{}, t, NM, NM, nop);
+  if (ragged) {   // the last tile: keys past L start from NEG_BIG (their K rows read as zero), so exp2 gives 0
+    const int tl = nkt - 1;
+    // one half's initial accumulators at a time (four blocks of both halves would not fit beside the stream); the
+    // second half's are written between the halves, long after the first half's chain starts read theirs
+    f32x16 M[NQB];
+    auto mk = [&](int hf) __attribute__((always_inline)) {
+      int Lo = L;
+      asm volatile("" : "+s"(Lo));   // (not before the stream so far)
+#pragma unroll
+      for (int qb = 0; qb < NQB; ++qb) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          M[qb][e] = tl * KT + 32 * hf + (e & 3) + 8 * (e >> 2) + 4 * h < Lo ? -m[qb] : NEG_BIG;
+        HS_OPAQUE(M[qb]);
+      }
+      asm volatile("s_nop 4" ::: "memory");
+    };
+    mk(0);
+    tile(ICR{}, tl, M, M, [&]() __attribute__((always_inline)) { mk(1); });
+  }
+  hs_vmcnt<0>();   // the last tiles' staging loads (past the end: zeros) retire before the exit
+  // the last query block of the last half: its wrapped VALU and its PV (and row-sum) MFMAs
+#pragma unroll
+  for (int g = 0; g < 10; ++g) {
+#pragma unroll
+    for (int op = 0; op < 4; ++op) valu_op(fw4_sched(g, op), NQB - 1);
+    if (g >= 4) {
+      asm volatile("s_nop 1" ::: "memory");
+      if (g == 6 || g == 9) rs_mfma(NQB - 1, g == 9);
+      else pv_mfma(g < 6 ? g - 4 : g - 5, NQB - 1, 1);   // the last half is a half 1
+    }
+  }
+  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) HS_OPAQUE(rs[qb]);   // read only after the last MFMAs completed
+
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {
+    const int q = qw0 + 32 * qb + r32;
+    // l of query 16 s + n sits in lane n, row s of the block's 16x16 accumulator (+ the last half's partials where
+    // the stream has not added them yet)
+    const float s0 = fw4_add_wraps(qb) ? lp[qb][0] + rs[qb][0] : lp[qb][0];
+    const float s1 = fw4_add_wraps(qb) ? lp[qb][1] + rs[qb][1] : lp[qb][1];
+    const float l0 = __shfl(s0, r32 & 15), l1 = __shfl(s1, r32 & 15);
+    const float lt = r32 < 16 ? l0 : l1;
+    if (q < L) {
+      const float inv = 1.f / lt;
+      bf16* op = a.out + b * a.bs_out + (long long)q * a.rs_out + hh * a.hs;
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          bf16x4 w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = to_bf16(o[qb][db][4 * g + j] * inv);
+          *(bf16x4*)(op + 32 * db + 8 * g + 4 * h) = w;
+        }
+      if (h == 0) a.lse2[((long long)b * a.H + hh) * L + q] = m[qb] + __log2f(lt);
+    }
+  }
+}
+
 }  // namespace lci
 
 // =============================================================================== C-ABI entry points
@@ -1478,8 +2065,32 @@ extern "C" long long lci_attn_fwd_ws_bytes(int B, int L, int H) {
   return (long long)B * H * ((L + KT - 1) / KT) * sizeof(float);
 }
 
-extern "C" int lci_attn_fwd(const void* qkv, void* out, float* lse2, float* knorm_ws, int B, int L, int H,
-                            int head_dim, float scale, void* stream) {
+// Which forward kernel serves a shape (0 = attn_fwd_hs_kernel, 1 = attn_fwd_hs4_kernel): the wide kernel only where
+// its grid of W workgroups both fills the chip and leaves no worse a tail than the narrow one's, i.e. W >= n_cu and
+// W / (ceil(W / n_cu) n_cu) >= 0.9. Pure host arithmetic (no device needed).
+extern "C" int lci_attn_fwd_pick(int B, int L, int H, int n_cu) {
+  if (B <= 0 || L <= 0 || H <= 0 || n_cu <= 0) return 0;
+  const long long W = (long long)B * H * ((L + FW4_QWG - 1) / FW4_QWG);
+  if (W < n_cu) return 0;
+  const long long rounds = (W + n_cu - 1) / n_cu;
+  return 10 * W >= 9 * rounds * n_cu ? 1 : 0;
+}
+
+static int attn_n_cu() {   // compute units of the current device, asked once per process
+  static const int n = [] {
+    int dev = 0, cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    return cu;
+  }();
+  return n;
+}
+
+// variant: -1 = lci_attn_fwd_pick, 0 = attn_fwd_hs_kernel, 1 = attn_fwd_hs4_kernel (for tests and A/B timing)
+extern "C" int lci_attn_fwd_variant(int variant, const void* qkv, void* out, float* lse2, float* knorm_ws, int B,
+                                    int L, int H, int head_dim, float scale, void* stream) {
+  LCI_CHECK(variant >= -1 && variant <= 1, "lci_attn_fwd_variant: variant %d (want -1, 0 or 1)", variant);
   LCI_CHECK(head_dim == DH, "lci_attn_fwd: head_dim %d unsupported (only 64)", head_dim);
   LCI_CHECK(B > 0 && L > 0 && H > 0, "lci_attn_fwd: bad shape B=%d L=%d H=%d", B, L, H);
   const int rs = 3 * H * DH;
@@ -1499,10 +2110,20 @@ extern "C" int lci_attn_fwd(const void* qkv, void* out, float* lse2, float* knor
   const int nkt = (L + KT - 1) / KT;
   hipLaunchKernelGGL(attn_key_norm_kernel, dim3((nkt + 3) / 4, H, B), dim3(256), 0, s, a, knorm_ws, nkt);
   LCI_LAUNCH_CHECK();
-  hipLaunchKernelGGL(attn_fwd_hs_kernel, dim3((L + HS_NW * 64 - 1) / (HS_NW * 64), H, B), dim3(HS_NW * 64), 0, s, a,
-                     (const float*)knorm_ws);
+  if (variant < 0) variant = lci_attn_fwd_pick(B, L, H, attn_n_cu());
+  if (variant == 1)
+    hipLaunchKernelGGL(attn_fwd_hs4_kernel, dim3((L + FW4_QWG - 1) / FW4_QWG, H, B), dim3(HS_NW * 64), 0, s, a,
+                       (const float*)knorm_ws);
+  else
+    hipLaunchKernelGGL(attn_fwd_hs_kernel, dim3((L + HS_NW * 64 - 1) / (HS_NW * 64), H, B), dim3(HS_NW * 64), 0, s, a,
+                       (const float*)knorm_ws);
   LCI_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int lci_attn_fwd(const void* qkv, void* out, float* lse2, float* knorm_ws, int B, int L, int H,
+                            int head_dim, float scale, void* stream) {
+  return lci_attn_fwd_variant(-1, qkv, out, lse2, knorm_ws, B, L, H, head_dim, scale, stream);
 }
 
 // backward workspace: (B, H, 2, L) f32 negated row constants [-lse2 | -delta], 256-B aligned

@@ -70,6 +70,23 @@ def attn_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
     return out, lse2
 
 
+def attn_fwd_variant(qkv: torch.Tensor, num_heads: int, scale: float, variant: int):
+    """attn_fwd with the forward kernel forced (include/lci.h lci_attn_fwd_variant: 0 = 64 queries per wave, 1 = 128,
+    -1 = the library's pick); for tests and A/B timing."""
+    _lib.require_gpu(qkv)
+    B, L, C = qkv.shape
+    dh = C // (3 * num_heads)
+    if qkv.dtype != torch.bfloat16:
+        raise _lib.LciError("attn_fwd_variant expects bf16 qkv")
+    out = torch.empty(B, L, num_heads * dh, device=qkv.device, dtype=torch.bfloat16)
+    lse2 = torch.empty(B, num_heads, L, device=qkv.device, dtype=torch.float32)
+    ws = torch.empty(_lib.load().lci_attn_fwd_ws_bytes(B, L, num_heads) // 4, device=qkv.device,
+                     dtype=torch.float32)
+    _lib.call("lci_attn_fwd_variant", int(variant), qkv.data_ptr(), out.data_ptr(), lse2.data_ptr(), ws.data_ptr(), B,
+              L, num_heads, dh, float(scale), _lib.stream_of(qkv))
+    return out, lse2
+
+
 def attn_bwd(qkv, out, dout, lse2, num_heads: int, scale: float):
     _lib.require_gpu(qkv, out, dout, lse2)
     B, L, C = qkv.shape

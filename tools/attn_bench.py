@@ -28,9 +28,23 @@ def main():
     ap.add_argument("--B", type=int, default=2)
     ap.add_argument("--H", type=int, default=6)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--fwd-variant", type=int, nargs="+", choices=[0, 1], default=None,
+                    help="time the forward alone with the kernel forced (0 = 64 queries per wave, 1 = 128); several "
+                         "values alternate in one process, --rounds times each")
+    ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     for L in a.L:
         qkv = torch.randn(a.B, L, 3 * a.H * 64, device="cuda").to(torch.bfloat16)
+        if a.fwd_variant is not None:
+            f = 4.0 * a.B * a.H * L * L * 64
+            for v in a.fwd_variant:   # warm both before the first timed round
+                kernels.attn_fwd_variant(qkv, a.H, 0.125, v)
+            for rnd in range(a.rounds):
+                for v in a.fwd_variant:
+                    tf = timeit(lambda: kernels.attn_fwd_variant(qkv, a.H, 0.125, v), a.iters)
+                    print(json.dumps({"L": L, "B": a.B, "H": a.H, "round": rnd, "fwd_variant": v,
+                                      "fwd_ms": round(tf, 3), "fwd_tflops": round(f / tf / 1e9, 1)}), flush=True)
+            continue
         dout = torch.randn(a.B, L, a.H * 64, device="cuda").to(torch.bfloat16)
         out, lse = kernels.attn_fwd(qkv, a.H, 0.125)
         tf = timeit(lambda: kernels.attn_fwd(qkv, a.H, 0.125), a.iters)

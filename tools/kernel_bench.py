@@ -48,12 +48,16 @@ def emit(name, ms, work, unit, cfg):
           flush=True)
 
 
-def bench_attention():
+def bench_attention(fwd_variant=None):
     B, H, L = 2, 6, 65536
     qkv = torch.randn(B, L, 3 * H * 64, device="cuda").to(torch.bfloat16)
     dout = torch.randn(B, L, H * 64, device="cuda").to(torch.bfloat16)
     out, lse = kernels.attn_fwd(qkv, H, 0.125)
     f = 4.0 * B * H * L * L * 64
+    if fwd_variant is not None:   # the forward alone with the kernel forced (0: 64 queries per wave, 1: 128)
+        emit(f"attn_fwd(variant {fwd_variant})", timeit(lambda: kernels.attn_fwd_variant(qkv, H, 0.125, fwd_variant)),
+             f, "TFLOP/s", f"B{B} H{H} L{L} d64")
+        return
     emit("attn_fwd", timeit(lambda: kernels.attn_fwd(qkv, H, 0.125)), f, "TFLOP/s", f"B{B} H{H} L{L} d64")
     emit("attn_bwd(3 launches)", timeit(lambda: kernels.attn_bwd(qkv, out, dout, lse, H, 0.125)), 2 * f, "TFLOP/s",
          f"B{B} H{H} L{L} d64")
@@ -398,9 +402,16 @@ def bench_loss():
 
 
 def main():
-    which = sys.argv[1:] or ["attention", "window", "scan", "fftconv", "patch", "linear", "mlp"]
+    argv, fwd_variant = sys.argv[1:], None
+    if "--fwd-variant" in argv:   # --fwd-variant {0,1}: the attention entry times that forward kernel alone
+        i = argv.index("--fwd-variant")
+        fwd_variant = int(argv[i + 1])
+        assert fwd_variant in (0, 1), "--fwd-variant takes 0 or 1"
+        del argv[i:i + 2]
+        argv = argv or ["attention"]
+    which = argv or ["attention", "window", "scan", "fftconv", "patch", "linear", "mlp"]
     if "attention" in which:
-        bench_attention()
+        bench_attention(fwd_variant)
     if "window" in which:
         bench_window()
     if "wstages" in which:
