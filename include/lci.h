@@ -62,8 +62,9 @@ extern "C" {
  * in the activation dtype; 27: lci_layernorm_bwd dxb; 28: lci_resample_cl_fwd, lci_resample1d_adj_ac; 29: lci_bn_relu_*; 30: lci_gemm_bt_acc;
  * 31: lci_layernorm_bwd dres2; 32: one-chunk selective scan without end-state workspaces (xend / xinit / sdt null),
  * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes);
- * 35: lci_attn_fwd_variant, lci_attn_fwd_pick. */
-#define LCI_ABI_VERSION 35
+ * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
+ * grows by the wide dQ kernel's per-workgroup flags. */
+#define LCI_ABI_VERSION 36
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -93,7 +94,10 @@ int lci_attn_fwd_variant(int variant, const void* qkv, void* out, float* lse2, f
 int lci_attn_fwd_pick(int B, int L, int H, int n_cu);
 /* dqkv (B, L, 3*H*64) bf16 <- dQ, dK, dV in the packed layout; dout (B, L, H*64) bf16;
  * delta_ws: 16-byte aligned workspace of lci_attn_bwd_ws_bytes(B, H, L) bytes, written by the call: the (B, H, 2, L)
- * f32 rows -lse2 | -delta (the backward kernels' row constants). No atomics: bitwise reproducible. */
+ * f32 rows -lse2 | -delta (the backward kernels' row constants) and, behind them at float offset B*H*2*L, the
+ * int32 flags [B][H][ceil(L / 512)] of the wide dQ kernel (written only when it runs: 1 = the workgroup of those 512
+ * queries found a lane whose four queries' lse2 lie more than 64 apart and left them to the 64-queries-per-wave
+ * stream, which a second launch runs for exactly those workgroups). No atomics: bitwise reproducible. */
 int lci_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, void* dqkv,
                  float* delta_ws, int B, int L, int H, int head_dim, float scale, void* stream);
 long long lci_attn_bwd_ws_bytes(int B, int H, int L);
@@ -101,6 +105,16 @@ long long lci_attn_bwd_ws_bytes(int B, int H, int L);
  * for timing. */
 int lci_attn_bwd_stage(int stage, const void* qkv, const void* out, const void* dout, const float* lse2,
                        void* dqkv, float* delta_ws, int B, int L, int H, int head_dim, float scale, void* stream);
+/* lci_attn_bwd_stage with the dQ kernel forced, for tests and A/B timing: dq_variant 0 = 64 queries per wave
+ * (attn_bwd_dq_hs_kernel), 1 = 128 queries per wave (attn_bwd_dq_hs4_kernel, then attn_bwd_dq_hsfb_kernel for the
+ * workgroups it flagged), -1 = what lci_attn_bwd and lci_attn_bwd_stage do: the choice of lci_attn_bwd_dq_pick for
+ * the current device's compute-unit count. dK / dV do not depend on it; flagged queries get variant 0's dQ bitwise. */
+int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, const void* out, const void* dout,
+                         const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H, int head_dim,
+                         float scale, void* stream);
+/* The dQ kernel lci_attn_bwd runs for a shape on a device of n_cu compute units (0 / 1 as above): the rule of
+ * lci_attn_fwd_pick (pure host arithmetic). */
+int lci_attn_bwd_dq_pick(int B, int L, int H, int n_cu);
 
 /* ViT attention in exact f32 products (csrc/attention_gen.hip): the reference's fp32 (non-AMP) SABlock path
  * (backbone_vit.py:191-201: fp32 einsums + softmax) and head dims 65..256 (the `custom` preset,

@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "liblci.so")
 LIB_PATH = os.environ.get("LCI_LIB_PATH", DEFAULT_LIB)   # override: kernel-variant A/B runs (no staleness check)
-ABI_VERSION = 35   # include/lci.h LCI_ABI_VERSION
+ABI_VERSION = 36  # include/lci.h LCI_ABI_VERSION
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -28,6 +28,7 @@ SIGNATURES = {
     "lci_attn_fwd_variant": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lci_attn_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lci_attn_bwd_stage": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
+    "lci_attn_bwd_variant": [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lci_attn_gen_fwd": [_I, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lci_attn_gen_bwd": [_I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "lci_patch_embed_fwd": [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P],
@@ -138,6 +139,8 @@ def load(path: str = LIB_PATH):
     lib.lci_attn_fwd_ws_bytes.argtypes = [_I, _I, _I]
     lib.lci_attn_fwd_pick.restype = ctypes.c_int
     lib.lci_attn_fwd_pick.argtypes = [_I, _I, _I, _I]
+    lib.lci_attn_bwd_dq_pick.restype = ctypes.c_int
+    lib.lci_attn_bwd_dq_pick.argtypes = [_I, _I, _I, _I]
     lib.lci_conv3_fwd_splits.restype = ctypes.c_int
     lib.lci_conv3_fwd_splits.argtypes = [ctypes.c_longlong, _I, _I, _I]
     lib.lci_conv3_wgrad_splits.restype = ctypes.c_longlong

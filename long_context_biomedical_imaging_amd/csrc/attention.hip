@@ -16,7 +16,10 @@
 // Backward:  (1) attn_bwd_delta_kernel: delta = rowsum(dO*O), written with -lse2 as the chains' row constants;
 //            (2) attn_bwd_dkdv_hs_kernel: 64 keys per wave on the lane, sweeps query tiles: S, dP recomputed,
 //            dV^T += dO^T.P, dK^T += Q^T.dS; (3) attn_bwd_dq_hs_kernel: 64 queries per wave, sweeps key tiles:
-//            S^T, dP^T, dQ^T += K^T.dS^T. No atomics: results are bitwise reproducible.
+//            S^T, dP^T, dQ^T += K^T.dS^T; where the grid still fills the chip (lci_attn_bwd_dq_pick, the forward's rule)
+//            attn_bwd_dq_hs4_kernel instead: 128 queries per wave on one shared softmax shift per lane, half the
+//            K | V staging, LDS reads and barriers per MFMA (workgroups whose lse2 spread forbids the shared shift
+//            are left to attn_bwd_dq_hsfb_kernel, the narrow stream). No atomics: results are bitwise reproducible.
 // Superseded variants (2 waves per SIMD, 16x16x32 shapes, d-major Q/dO staging, MFMA row sums, timing probes) were
 // removed in round 5; their same-box A/B records are kept in profiles/r0[1-4]_attn_*.
 #include "common.hpp"
@@ -191,6 +194,22 @@ __device__ __forceinline__ void hs_st16(unsigned addr, const u32x4& v) {
 template <int OFF>
 __device__ __forceinline__ void hs_st4(unsigned addr, uint32_t v) {
   asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "a"(v), "i"(OFF) : "memory");
+}
+// the same from / to arch VGPRs, for a kernel whose AGPR half is full (attn_bwd_dq_hs4_kernel)
+__device__ __forceinline__ u32x4 hs_ld16v(rsrc_t r, int voff, int soff) {
+  u32x4 v;
+  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(v) : "v"(voff), "s"(r), "s"(soff) : "memory");
+  return v;
+}
+template <int OFF>
+__device__ __forceinline__ void hs_st16v(unsigned addr, const u32x4& v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "i"(OFF) : "memory");
+}
+// f(integral_constant<int, g>) for every gap g of a half, unrolled by pack expansion (a `#pragma unroll` loop of 40+
+// gaps of a placed stream is past the loop unroller's limit and silently stays a loop)
+template <class F, int... G>
+__device__ __forceinline__ void hs_for_gaps(F&& f, std::integer_sequence<int, G...>) {
+  (f(std::integral_constant<int, G>{}), ...);
 }
 // Row constants of the next half by DPP (LCI_DKDV_DPPRC=1): one ds_read_b32 per constant row set (lane l holds the
 // constant of register l & 15 of its half-wave) and 16 v_mov_b32_dpp row_newbcast:i per set, instead of eight
@@ -680,7 +699,8 @@ constexpr unsigned char DQ_SCHED[24][4] = {
 #define LCI_DQ_EARLY 1
 #endif
 constexpr bool DQ_EARLY = LCI_DQ_EARLY != 0;
-__global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs a) {
+// (the body of attn_bwd_dq_hs_kernel and of attn_bwd_dq_hsfb_kernel, the wide kernel's fallback, below)
+__device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
   constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
   constexpr int SLOT_B = 2 * TILE_B;                // K | V
   constexpr int NSLOT = 4;
@@ -743,10 +763,10 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs 
   const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
   auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
     const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rk, dk0, t * KT * rs2k, sb + 2048 * wave);
-    if (i == 1) hs_dma16(rk, dk1, t * KT * rs2k, sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rv, dv0, t * KT * rs2v, sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rv, dv1, t * KT * rs2v, sb + TILE_B + 2048 * wave + 1024);
+    if (i == 0) hs_dma16(rk, dk0, (int)((uint32_t)t * KT * rs2k), sb + 2048 * wave);
+    if (i == 1) hs_dma16(rk, dk1, (int)((uint32_t)t * KT * rs2k), sb + 2048 * wave + 1024);
+    if (i == 2) hs_dma16(rv, dv0, (int)((uint32_t)t * KT * rs2v), sb + TILE_B + 2048 * wave);
+    if (i == 3) hs_dma16(rv, dv1, (int)((uint32_t)t * KT * rs2v), sb + TILE_B + 2048 * wave + 1024);
   };
 
   // LDS byte offsets of every distinct fragment read within a ring slot, computed once and kept opaque (see the
@@ -863,10 +883,10 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs 
   u32x4 stg[4];
   const unsigned wst = lds0 + 2048 * wave + 16 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) stg[0] = hs_ld16(rk, dk0, t * KT * rs2k);
-    if (i == 1) stg[1] = hs_ld16(rk, dk1, t * KT * rs2k);
-    if (i == 2) stg[2] = hs_ld16(rv, dv0, t * KT * rs2v);
-    if (i == 3) stg[3] = hs_ld16(rv, dv1, t * KT * rs2v);
+    if (i == 0) stg[0] = hs_ld16(rk, dk0, (int)((uint32_t)t * KT * rs2k));
+    if (i == 1) stg[1] = hs_ld16(rk, dk1, (int)((uint32_t)t * KT * rs2k));
+    if (i == 2) stg[2] = hs_ld16(rv, dv0, (int)((uint32_t)t * KT * rs2v));
+    if (i == 3) stg[3] = hs_ld16(rv, dv1, (int)((uint32_t)t * KT * rs2v));
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging registers; wait, publish tile 0; K rows of half 0
   dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
@@ -928,6 +948,12 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs 
     }
   }
   asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+  // the accumulators are read only after the last MFMAs completed: without this the compiler may move its
+  // v_accvgpr_read above the s_nops (nothing else orders them)
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) asm volatile("" : "+a"(dq[i][j]));
 
   const float sc = a.scale;
   // the lane's query re-derived here, not kept from the prologue: hoisted out of the loop, the epilogue's row
@@ -948,6 +974,437 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs 
 #pragma unroll
           for (int j = 0; j < 4; ++j) w[j] = to_bf16(dq[db][qb][4 * g + j] * sc);
           *(bf16x4*)(dqp + 32 * db + 8 * g + 4 * h) = w;
+        }
+    }
+  }
+}
+
+__global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs_kernel(AttnArgs a) { attn_bwd_dq_hs_body(a); }
+
+// ---------------------------------------------------- backward: dQ kernel with 128 queries per wave (the wide dQ)
+// attn_bwd_dq_hs_kernel's stream with four query blocks of 32 per wave (512 queries per workgroup): the 16 fragment
+// reads of a 32-key half (4 K rows, 4 V rows, 8 transposed K halves), the tile's barrier, staging wait, four loads
+// and four LDS stores feed 48 MFMAs instead of 24. Per half 48 gaps: block b's S~^T / dP^T chains at 12b .. 12b+7,
+// the dQ^T MFMAs of block b-1 at 12b+8 .. 12b+11 (block 0's gaps: block 3 of the previous half); the S / dP / pack
+// registers alternate between two sets (block b uses set b & 1, free again when block b+2's chains start); the VALU
+// of each gap from DQ4_SCHED (tools/gen_dq_sched.py --nqb 4). LDS reads: transposed K at gaps 12-19 (before block 0's
+// dQ^T at 20, after block 3's of the previous half at 8-11), the next half's K rows at 40-43 and V rows at 44-47
+// (each 4 gaps after the last chain's read of the fragment).
+// Registers: dQ^T 128 + Q~ 64 + dO 64 fill the AGPR half, so the staging registers are arch VGPRs, and the four
+// -lse2 splats the narrow layout would need (64 registers) are one: with the query on the MFMA lane a per-query
+// factor leaves the key sum,
+//   dQ^T[d][q] = 2^(u - lse2_q) sum_k K^T[d][k] bf16(exp2(S~[k][q] - u) (dP[k][q] - delta_q))   for any per-lane u;
+// u = the largest lse2 among the lane's (up to) four queries, so every exp2 is <= 1, all four S~ chains start from
+// the one splat -u, and 2^(u - lse2_q) joins `scale` in the epilogue. -delta_q stays a per-block initial accumulator.
+// A lane's spread u - lse2_q is bounded by SAFE_EXP2 = 64 (the forward's fixed-reference criterion: 2^63 of room
+// before an f32 or bf16 under- or overflows): a workgroup with a lane past it writes 1 to its entry of the flag
+// array behind the row constants (dq4_flags; every other workgroup writes 0) and returns, and
+// attn_bwd_dq_hsfb_kernel, launched after it, runs the narrow stream for the flagged workgroups' queries.
+constexpr int DQ4_NQB = 4;
+constexpr int DQ4_NG = 12 * DQ4_NQB;          // gaps per half
+constexpr int DQ4_QWG = HS_NW * 32 * DQ4_NQB;   // queries per workgroup
+// gap  0: E3.8 E3.9
+// gap  1: M3.8 M3.9 E3.10 C3.4
+// gap  2: M3.10 E3.11 E3.12
+// gap  3: M3.11 M3.12 C3.5 E3.13
+// gap  4: E3.14 M3.13 E3.15 C3.6
+// gap  5: M3.14 M3.15 E0.0 C3.7
+// gap  6: E0.1 E0.2
+// gap  7: E0.3 E0.4
+// gap  8: E0.5 E0.6
+// gap  9: M0.0 M0.1 M0.2 M0.3
+// gap 10: C0.0 C0.1 M0.4 M0.5
+// gap 11: M0.6 C0.2 E0.7 E0.8
+// gap 12: M0.7 M0.8 C0.3 E0.9
+// gap 13: E0.10 M0.9 E0.11 C0.4
+// gap 14: M0.10 M0.11 E0.12 C0.5
+// gap 15: M0.12 E0.13 E0.14
+// gap 16: M0.13 M0.14 C0.6 E0.15
+// gap 17: E1.0 M0.15 E1.1 C0.7
+// gap 18: E1.2 E1.3
+// gap 19: E1.4 E1.5
+// gap 20: E1.6 E1.7
+// gap 21: M1.0 M1.1 M1.2 M1.3
+// gap 22: C1.0 C1.1 M1.4 M1.5
+// gap 23: M1.6 M1.7 C1.2 C1.3
+// gap 24: E1.8 E1.9
+// gap 25: M1.8 M1.9 E1.10 C1.4
+// gap 26: M1.10 E1.11 E1.12
+// gap 27: M1.11 M1.12 C1.5 E1.13
+// gap 28: E1.14 M1.13 E1.15 C1.6
+// gap 29: E2.0 E2.1 M1.14 M1.15
+// gap 30: E2.2 E2.3 C1.7
+// gap 31: E2.4 E2.5
+// gap 32: E2.6 E2.7
+// gap 33: M2.0 M2.1 M2.2 M2.3
+// gap 34: C2.0 C2.1 M2.4 M2.5
+// gap 35: M2.6 M2.7 C2.2 C2.3
+// gap 36: E2.8 E2.9
+// gap 37: M2.8 M2.9 E2.10 C2.4
+// gap 38: M2.10 E2.11 E2.12
+// gap 39: M2.11 M2.12 C2.5 E2.13
+// gap 40: E2.14 M2.13 E2.15 C2.6
+// gap 41: E3.0 E3.1 M2.14 M2.15
+// gap 42: E3.2 E3.3 C2.7
+// gap 43: E3.4 E3.5
+// gap 44: E3.6 E3.7
+// gap 45: M3.0 M3.1 M3.2 M3.3
+// gap 46: C3.0 C3.1 M3.4 M3.5
+// gap 47: M3.6 M3.7 C3.2 C3.3
+constexpr unsigned char DQ4_SCHED[48][4] = {
+    {0x38, 0x39, 0xff, 0xff},
+    {0x78, 0x79, 0x3a, 0xb4},
+    {0x7a, 0x3b, 0x3c, 0xff},
+    {0x7b, 0x7c, 0xb5, 0x3d},
+    {0x3e, 0x7d, 0x3f, 0xb6},
+    {0x7e, 0x7f, 0x00, 0xb7},
+    {0x01, 0x02, 0xff, 0xff},
+    {0x03, 0x04, 0xff, 0xff},
+    {0x05, 0x06, 0xff, 0xff},
+    {0x40, 0x41, 0x42, 0x43},
+    {0x80, 0x81, 0x44, 0x45},
+    {0x46, 0x82, 0x07, 0x08},
+    {0x47, 0x48, 0x83, 0x09},
+    {0x0a, 0x49, 0x0b, 0x84},
+    {0x4a, 0x4b, 0x0c, 0x85},
+    {0x4c, 0x0d, 0x0e, 0xff},
+    {0x4d, 0x4e, 0x86, 0x0f},
+    {0x10, 0x4f, 0x11, 0x87},
+    {0x12, 0x13, 0xff, 0xff},
+    {0x14, 0x15, 0xff, 0xff},
+    {0x16, 0x17, 0xff, 0xff},
+    {0x50, 0x51, 0x52, 0x53},
+    {0x90, 0x91, 0x54, 0x55},
+    {0x56, 0x57, 0x92, 0x93},
+    {0x18, 0x19, 0xff, 0xff},
+    {0x58, 0x59, 0x1a, 0x94},
+    {0x5a, 0x1b, 0x1c, 0xff},
+    {0x5b, 0x5c, 0x95, 0x1d},
+    {0x1e, 0x5d, 0x1f, 0x96},
+    {0x20, 0x21, 0x5e, 0x5f},
+    {0x22, 0x23, 0x97, 0xff},
+    {0x24, 0x25, 0xff, 0xff},
+    {0x26, 0x27, 0xff, 0xff},
+    {0x60, 0x61, 0x62, 0x63},
+    {0xa0, 0xa1, 0x64, 0x65},
+    {0x66, 0x67, 0xa2, 0xa3},
+    {0x28, 0x29, 0xff, 0xff},
+    {0x68, 0x69, 0x2a, 0xa4},
+    {0x6a, 0x2b, 0x2c, 0xff},
+    {0x6b, 0x6c, 0xa5, 0x2d},
+    {0x2e, 0x6d, 0x2f, 0xa6},
+    {0x30, 0x31, 0x6e, 0x6f},
+    {0x32, 0x33, 0xa7, 0xff},
+    {0x34, 0x35, 0xff, 0xff},
+    {0x36, 0x37, 0xff, 0xff},
+    {0x70, 0x71, 0x72, 0x73},
+    {0xb0, 0xb1, 0x74, 0x75},
+    {0x76, 0x77, 0xb2, 0xb3}};
+static_assert(sizeof(DQ4_SCHED) == DQ4_NG * 4, "one row per gap");
+__host__ __device__ constexpr unsigned char dq4_sched(int g, int o) { return DQ4_SCHED[g][o]; }
+
+// per-workgroup flags of the wide dQ kernel, behind the (B, H, 2, L) row constants of the backward workspace:
+// int32 [B][H][ceil(L / DQ4_QWG)], 1 = the workgroup left its queries to attn_bwd_dq_hsfb_kernel
+__host__ __device__ inline long long dq4_flag_offset(int B, int H, int L) { return (long long)B * H * 2 * L; }   // floats
+__device__ __forceinline__ int* dq4_flag(const AttnArgs& a, int wg, int hh, int b, int B) {
+  const int nwg = (a.L + DQ4_QWG - 1) / DQ4_QWG;
+  return (int*)(a.delta + dq4_flag_offset(B, a.H, a.L)) + ((long long)b * a.H + hh) * nwg + wg;
+}
+
+// the narrow stream for the queries of flagged wide workgroups (same grid as attn_bwd_dq_hs_kernel; two of its
+// workgroups per wide one): their dQ is bitwise attn_bwd_dq_hs_kernel's
+__global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hsfb_kernel(AttnArgs a) {
+  if (*dq4_flag(a, blockIdx.x / (DQ4_QWG / (HS_NW * 64)), blockIdx.y, blockIdx.z, gridDim.z) == 0) return;
+  attn_bwd_dq_hs_body(a);
+}
+
+__global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs a) {
+  constexpr int NQB = DQ4_NQB;
+  constexpr int NG = DQ4_NG;
+  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
+  constexpr int SLOT_B = 2 * TILE_B;                // K | V
+  constexpr int HALF_B = 32 * DH * 2;               // rows 32-63 of a tile: sw128 is invariant under 16-row steps
+  constexpr int NSLOT = 4;
+  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
+  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ int flagged_wg;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hh = blockIdx.y, b = blockIdx.z;
+  const int L = a.L;
+  const int h = lane >> 5, r32 = lane & 31;
+  const int qw0 = blockIdx.x * DQ4_QWG + wave * (32 * NQB);
+  const int nkt = (L + KT - 1) / KT;
+  const int nkt4 = (nkt + 3) & ~3;
+  if (tid == 0) flagged_wg = 0;
+
+  // the row constants of the lane's four queries: -u = the smallest -lse2 among those below L, and the spread guard
+  f32x16 NU, ND[NQB];
+  {
+    const float* ws = a.delta + ((long long)b * a.H + hh) * 2 * L;
+    float lo = -NEG_BIG, hi = NEG_BIG;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      const int q = qw0 + 32 * qb + r32;
+      float nd = 0.f;
+      if (q < L) {
+        const float nl = ws[q];
+        nd = ws[L + q];
+        lo = fminf(lo, nl);
+        hi = fmaxf(hi, nl);
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) ND[qb][i] = nd;
+    }
+    const bool ok = hi - lo <= SAFE_EXP2;   // (a lane with no query: -2e30)
+    const float nu = hi >= lo ? lo : 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) NU[i] = nu;
+    __syncthreads();
+    if (!__all(ok) && lane == 0) flagged_wg = 1;
+    __syncthreads();
+    const int flagged = __builtin_amdgcn_readfirstlane(flagged_wg);
+    if (tid == 0) *dq4_flag(a, blockIdx.x, hh, b, gridDim.z) = flagged;
+    if (flagged) return;
+  }
+  HS_OPAQUE(NU);
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) HS_OPAQUE(ND[qb]);
+
+  // Q~ / dO as B operands: lane holds X[qw0 + 32qb + r32][16ks + 8h + j] (Q prescaled into the exp2 domain)
+  bf16x8 qf[NQB][4], df[NQB][4];
+  {
+    const bf16* qp = a.q + b * a.bs_q + hh * a.hs;
+    const bf16* dop = a.dout + b * a.bs_do + hh * a.hs;
+#pragma unroll
+    for (int qb = 0; qb < NQB; ++qb) {
+      const int q = qw0 + 32 * qb + r32;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        if (q < L) {
+          qf[qb][ks] = *(const bf16x8*)(qp + (long long)q * a.rs_q + 16 * ks + 8 * h);
+          df[qb][ks] = *(const bf16x8*)(dop + (long long)q * a.rs_do + 16 * ks + 8 * h);
+        } else {
+          qf[qb][ks] = bf16x8{};
+          df[qb][ks] = bf16x8{};
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[qb][ks][j] = to_bf16(to_f32(qf[qb][ks][j]) * a.c);
+      }
+      hs_vmcnt<0>();   // (no compiler vmcnt wait inside the loop; per block: the fragments go to AGPRs at once)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) { HS_TO_AGPR(qf[qb][ks]); HS_TO_AGPR(df[qb][ks]); }
+    }
+  }
+
+  // ---- K / V tile pieces (wave w: rows 16w .. 16w+15 of each, 1-KB pieces of 8 rows): tile 0 by LDS-DMA
+  const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
+  const rsrc_t rk = make_rsrc(a.k + b * a.bs_k + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2k + DH * 2);
+  const rsrc_t rv = make_rsrc(a.v + b * a.bs_v + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2v + DH * 2);
+  const int prow = lane >> 3;
+  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
+  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
+  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
+  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
+  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
+  // byte offset of tile t's pieces: unsigned, tiles up to nkt4 + 1 are addressed (past L: out of range, zeros)
+  auto toff = [&](int t, int rs2) __attribute__((always_inline)) { return (int)((uint32_t)t * KT * (uint32_t)rs2); };
+  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
+    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
+    if (i == 0) hs_dma16(rk, dk0, toff(t, rs2k), sb + 2048 * wave);
+    if (i == 1) hs_dma16(rk, dk1, toff(t, rs2k), sb + 2048 * wave + 1024);
+    if (i == 2) hs_dma16(rv, dv0, toff(t, rs2v), sb + TILE_B + 2048 * wave);
+    if (i == 3) hs_dma16(rv, dv1, toff(t, rs2v), sb + TILE_B + 2048 * wave + 1024);
+  };
+
+  // LDS byte offsets of the fragment reads of rows 0-31 within a ring slot (opaque lane registers, as the narrow
+  // kernel's); rows 32-63 and the ring slot are DS immediates
+  unsigned row_off[4], tr_off[4][2];   // [k-step | fragment][part]
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    row_off[k] = 2 * sw128(r32, 16 * k + 8 * h);
+    HS_OPAQUE(row_off[k]);
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {   // fragment k = (d block k & 1, k-step k >> 1)
+      const int rw = 16 * (k >> 1) + 4 * h + ((lane & 15) >> 2) + 8 * part;
+      const int col = 32 * (k & 1) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+      tr_off[k][part] = 2 * sw128(rw, col);
+      HS_OPAQUE(tr_off[k][part]);
+    }
+  }
+  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {   // soff: slot (+ TILE_B for V) bytes
+    return *(const bf16x8*)(smem + row_off[ks] + (soff + r0i * HALF_B));
+  };
+  auto trh = [&](int soff, int r0i, int f, int part) __attribute__((always_inline)) {
+    return lds_tr4((const bf16*)(smem + tr_off[f][part] + (soff + r0i * HALF_B)));
+  };
+
+  f32x16 dq[2][NQB];           // [d block][query block]: dQ^T, lane = query, rows d = 32db + (i&3) + 8(i>>2) + 4h
+  f32x16 S[2], P[2];           // [set]: S~^T - u, dP^T - delta (rows = the half's 32 keys)
+  u32x4 dsp[2][2];             // [set][k-step] bf16 dS^T packs
+  bf16x4 ktr[2][2][2];         // [d block][k-step][half of the fragment] transposed K (keys as the k index)
+  // zeros: the first half's gaps 0-11 run block 3 of a half that does not exist (set 1: dS = exp2(0) * 0)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    S[i] = P[i] = f32x16{};
+    HS_OPAQUE(S[i]);
+    HS_OPAQUE(P[i]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      dsp[i][j] = u32x4{};
+      HS_OPAQUE(dsp[i][j]);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) { ktr[i][j][k] = bf16x4{}; HS_OPAQUE(ktr[i][j][k]); }
+    }
+#pragma unroll
+    for (int j = 0; j < NQB; ++j) { dq[i][j] = f32x16{}; HS_TO_AGPR(dq[i][j]); }
+  }
+  bf16x8 kr[4], vr[4];         // K / V row fragments (A operands of the chains)
+
+  auto valu_op = [&](unsigned char c, int only_qb) __attribute__((always_inline)) {
+    if (c == 0xFF) return;
+    const int kind = c >> 6, qb = (c >> 4) & 3, st = qb & 1, i = c & 15;
+    if (only_qb >= 0 && qb != only_qb) return;
+    if (kind == 0) HS_EXP(S[st][i]);
+    else if (kind == 1) HS_MUL(P[st][i], S[st][i]);
+    else HS_CVT(dsp[st][i >> 2][i & 3], P[st][2 * i], P[st][2 * i + 1]);
+  };
+  // k = 0..3: (d block k & 1, k-step k >> 1)
+  auto dq_mfma = [&](int k, int qb) __attribute__((always_inline)) {
+    const int db = k & 1, s2 = k >> 1;
+    HS_MFMA_G(dq[db][qb], cat44(ktr[db][s2][0], ktr[db][s2][1]), __builtin_bit_cast(bf16x8, dsp[qb & 1][s2]));
+  };
+  auto mfma_gap = [&](int g) __attribute__((always_inline)) {
+    const int bq = g / 12, r = g % 12, st = bq & 1;
+    if (r < 4) {
+      if (r == 0) HS_MFMA_C0(S[st], kr[0], qf[bq][0], NU); else HS_MFMA_C(S[st], kr[r], qf[bq][r]);
+    } else if (r < 8) {
+      if (r == 4) HS_MFMA_C0(P[st], vr[0], df[bq][0], ND[bq]); else HS_MFMA_C(P[st], vr[r - 4], df[bq][r - 4]);
+    } else {
+      dq_mfma(r - 8, (bq + NQB - 1) % NQB);
+    }
+  };
+
+  // One 32-key half (rows r0i of slot soff); the next half's rows are rows nr0i of slot nsoff
+  constexpr int KR0 = NG - 8, VR0 = NG - 4;
+  auto half = [&](int soff, int r0i, int nsoff, int nr0i, auto hook) __attribute__((always_inline)) {
+    hs_for_gaps([&](auto G) __attribute__((always_inline)) {
+      constexpr int g = decltype(G)::value;
+      mfma_gap(g);
+      // gap 12b+9 multiplies the dP^T chain of block b (last MFMA at 12b+7): 12 wait states by instruction count
+      if (g % 12 == 9) asm volatile("s_nop 5" ::: "memory");
+      valu_op(dq4_sched(g, 0), -1);
+      valu_op(dq4_sched(g, 1), -1);
+      valu_op(dq4_sched(g, 2), -1);
+      valu_op(dq4_sched(g, 3), -1);
+      if constexpr (g >= 12 && g < 20) {
+        constexpr int f = (g - 12) >> 1, part = (g - 12) & 1;
+        ktr[f & 1][f >> 1][part] = trh(soff, r0i, f, part);
+      } else if constexpr (g >= KR0 && g < KR0 + 4) {
+        kr[g - KR0] = row(nsoff, nr0i, g - KR0);
+      } else if constexpr (g >= VR0) {
+        vr[g - VR0] = row(nsoff + TILE_B, nr0i, g - VR0);
+      }
+      hook(g);
+    }, std::make_integer_sequence<int, NG>{});
+  };
+
+  // register staging as the narrow kernel's, in arch VGPRs: tile t+1's pieces (loaded during tile t-1) are stored at
+  // gaps 1-7 of tile t's half 0, tile t+2's loaded at gaps 9-15; half 1's barrier publishes t+1
+  u32x4 stg[4];
+  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
+    if (i == 0) stg[0] = hs_ld16v(rk, dk0, toff(t, rs2k));
+    if (i == 1) stg[1] = hs_ld16v(rk, dk1, toff(t, rs2k));
+    if (i == 2) stg[2] = hs_ld16v(rv, dv0, toff(t, rs2v));
+    if (i == 3) stg[3] = hs_ld16v(rv, dv1, toff(t, rs2v));
+  };
+  // prologue: tile 0 by LDS-DMA, tile 1 into the staging registers; wait, publish tile 0; K / V rows of half 0
+  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
+  hs_vmcnt<0>();
+  __builtin_amdgcn_s_barrier();
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    kr[ks] = row(0, 0, ks);
+    vr[ks] = row(TILE_B, 0, ks);
+  }
+  __builtin_amdgcn_s_waitcnt(LGKM0_WAIT);
+
+  auto tile = [&](auto SL, int t) __attribute__((always_inline)) {   // tile t sits in ring slot SL (DS immediates)
+    constexpr int sl = decltype(SL)::value;
+    constexpr int soff = sl * SLOT_B, nsoff = ((sl + 1) & (NSLOT - 1)) * SLOT_B;
+    // tile t+1 is published at gap 6 of half 1 (its first reader: the K rows at gaps 40-43)
+    auto stage = [&](int g) __attribute__((always_inline)) {
+      if (t + 1 < nkt4 && g == 6) __builtin_amdgcn_s_barrier();
+    };
+    auto stage0 = [&](int g) __attribute__((always_inline)) {
+      if (g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
+      if (g < 8 && (g & 1)) {
+        switch (g) {
+          case 1: hs_st16v<nsoff>(wst, stg[0]); break;
+          case 3: hs_st16v<nsoff + 1024>(wst, stg[1]); break;
+          case 5: hs_st16v<nsoff + TILE_B>(wst, stg[2]); break;
+          default: hs_st16v<nsoff + TILE_B + 1024>(wst, stg[3]); break;
+        }
+      } else if (g >= 9 && g < 16 && (g & 1)) {
+        ld_piece(t + 2, (g - 9) >> 1);
+      }
+    };
+    half(soff, 0, soff, 1, stage0);
+    half(soff, 1, nsoff, 0, stage);
+  };
+  // key tiles padded to a multiple of 4, as the narrow kernel: zero K rows past L add nothing to dQ^T
+  for (int t = 0; t < nkt4; t += 4) {   // t & 3 == 0 here
+    tile(std::integral_constant<int, 0>{}, t);
+    tile(std::integral_constant<int, 1>{}, t + 1);
+    tile(std::integral_constant<int, 2>{}, t + 2);
+    tile(std::integral_constant<int, 3>{}, t + 3);
+  }
+  hs_vmcnt<0>();   // the last tiles' staging loads (past the end: zeros) retire
+  // query block 3 of the last half: its remaining VALU (wrapped into gaps 0-5) and its dQ^T
+#pragma unroll
+  for (int g = 0; g < 12; ++g) {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) valu_op(dq4_sched(g, o), NQB - 1);
+    if (g >= 8) {
+      asm volatile("s_nop 1" ::: "memory");
+      dq_mfma(g - 8, NQB - 1);
+    }
+  }
+  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {   // read only after the last MFMAs completed
+    asm volatile("" : "+a"(dq[0][qb]));
+    asm volatile("" : "+a"(dq[1][qb]));
+  }
+
+  // dQ = scale 2^(u - lse2_q) dQ^T. The lane's queries and row constants are re-derived here, not kept across the loop
+  unsigned lane_e;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+  const int r32e = (int)lane_e & 31, he = (int)lane_e >> 5;
+  const float* wse = a.delta + ((long long)b * a.H + hh) * 2 * L;
+  float nle[NQB], lo = -NEG_BIG;
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {
+    const int q = qw0 + 32 * qb + r32e;
+    nle[qb] = q < L ? wse[q] : -NEG_BIG;
+    lo = fminf(lo, nle[qb]);
+  }
+#pragma unroll
+  for (int qb = 0; qb < NQB; ++qb) {
+    const int q = qw0 + 32 * qb + r32e;
+    if (q < L) {
+      const float sc = a.scale * exp2_fast(nle[qb] - lo);   // u - lse2_q = (-lse2_q) - (-u), in [0, 64]
+      bf16* dqp = a.out + b * a.bs_out + (long long)q * a.rs_out + hh * a.hs;
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          bf16x4 w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = to_bf16(dq[db][qb][4 * g + j] * sc);
+          *(bf16x4*)(dqp + 32 * db + 8 * g + 4 * he) = w;
         }
     }
   }
@@ -1578,11 +2035,6 @@ __host__ __device__ constexpr bool fw4_wrapped_exp(int i) {
 // a block's row-sum adds run in the half after its row-sum MFMAs (true) or in the same half (false)
 __host__ __device__ constexpr bool fw4_add_wraps(int qb) { return 10 * qb + 22 >= FW4_NG; }
 
-template <class F, int... G>
-__device__ __forceinline__ void hs_for_gaps(F&& f, std::integer_sequence<int, G...>) {
-  (f(std::integral_constant<int, G>{}), ...);
-}
-
 __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a, const float* knorm) {
   constexpr int NQB = FW4_NQB;
   constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
@@ -2068,13 +2520,16 @@ extern "C" long long lci_attn_fwd_ws_bytes(int B, int L, int H) {
 // Which forward kernel serves a shape (0 = attn_fwd_hs_kernel, 1 = attn_fwd_hs4_kernel): the wide kernel only where
 // its grid of W workgroups both fills the chip and leaves no worse a tail than the narrow one's, i.e. W >= n_cu and
 // W / (ceil(W / n_cu) n_cu) >= 0.9. Pure host arithmetic (no device needed).
-extern "C" int lci_attn_fwd_pick(int B, int L, int H, int n_cu) {
+static int attn_wide_pick(int B, int L, int H, int n_cu, int qwg) {   // qwg: queries per wide workgroup
   if (B <= 0 || L <= 0 || H <= 0 || n_cu <= 0) return 0;
-  const long long W = (long long)B * H * ((L + FW4_QWG - 1) / FW4_QWG);
+  const long long W = (long long)B * H * ((L + qwg - 1) / qwg);
   if (W < n_cu) return 0;
   const long long rounds = (W + n_cu - 1) / n_cu;
   return 10 * W >= 9 * rounds * n_cu ? 1 : 0;
 }
+extern "C" int lci_attn_fwd_pick(int B, int L, int H, int n_cu) { return attn_wide_pick(B, L, H, n_cu, FW4_QWG); }
+// The same rule for the dQ kernel of the backward (0 = attn_bwd_dq_hs_kernel, 1 = attn_bwd_dq_hs4_kernel)
+extern "C" int lci_attn_bwd_dq_pick(int B, int L, int H, int n_cu) { return attn_wide_pick(B, L, H, n_cu, DQ4_QWG); }
 
 static int attn_n_cu() {   // compute units of the current device, asked once per process
   static const int n = [] {
@@ -2095,7 +2550,8 @@ extern "C" int lci_attn_fwd_variant(int variant, const void* qkv, void* out, flo
   LCI_CHECK(B > 0 && L > 0 && H > 0, "lci_attn_fwd: bad shape B=%d L=%d H=%d", B, L, H);
   const int rs = 3 * H * DH;
   LCI_CHECK(check_packed(qkv, rs) && check_packed(out, H * DH), "lci_attn_fwd: misaligned pointers");
-  LCI_CHECK((long long)(L + 4 * KT) * rs * 2 < (1ll << 31), "lci_attn_fwd: L=%d too long for 32-bit buffer offsets", L);
+  // the placed kernels stage key tiles up to two past the tile count padded to a multiple of 4: rows below L + 6 KT
+  LCI_CHECK((long long)(L + 6 * KT) * rs * 2 < (1ll << 31), "lci_attn_fwd: L=%d too long for 32-bit buffer offsets", L);
   LCI_CHECK(knorm_ws != nullptr, "lci_attn_fwd: knorm_ws (lci_attn_fwd_ws_bytes) is required");
   AttnArgs a{};
   const bf16* base = (const bf16*)qkv;
@@ -2126,22 +2582,27 @@ extern "C" int lci_attn_fwd(const void* qkv, void* out, float* lse2, float* knor
   return lci_attn_fwd_variant(-1, qkv, out, lse2, knorm_ws, B, L, H, head_dim, scale, stream);
 }
 
-// backward workspace: (B, H, 2, L) f32 negated row constants [-lse2 | -delta], 256-B aligned
+// backward workspace: (B, H, 2, L) f32 negated row constants [-lse2 | -delta], then the wide dQ kernel's int32 flags
+// [B][H][ceil(L / 512)] (dq4_flag_offset), 256-B aligned
 extern "C" long long lci_attn_bwd_ws_bytes(int B, int H, int L) {
-  return ((long long)B * H * 2 * L * 4 + 255) / 256 * 256;
+  const long long flags = (long long)B * H * ((L + DQ4_QWG - 1) / DQ4_QWG);
+  return ((dq4_flag_offset(B, H, L) + flags) * 4 + 255) / 256 * 256;
 }
 
-// stage: -1 = all three launches; 0 = delta, 1 = dK/dV, 2 = dQ (for per-kernel timing)
-extern "C" int lci_attn_bwd_stage(int stage, const void* qkv, const void* out, const void* dout, const float* lse2,
-                                  void* dqkv, float* delta_ws, int B, int L, int H, int head_dim, float scale,
-                                  void* stream) {
+// dq_variant: -1 = lci_attn_bwd_dq_pick, 0 = attn_bwd_dq_hs_kernel, 1 = attn_bwd_dq_hs4_kernel + its fallback launch;
+// stage: -1 = all launches; 0 = delta, 1 = dK/dV, 2 = dQ (for per-kernel timing)
+extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, const void* out, const void* dout,
+                                    const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H, int head_dim,
+                                    float scale, void* stream) {
+  LCI_CHECK(dq_variant >= -1 && dq_variant <= 1, "lci_attn_bwd_variant: dq_variant %d (want -1, 0 or 1)", dq_variant);
   LCI_CHECK(head_dim == DH, "lci_attn_bwd: head_dim %d unsupported (only 64)", head_dim);
   LCI_CHECK(B > 0 && L > 0 && H > 0, "lci_attn_bwd: bad shape B=%d L=%d H=%d", B, L, H);
   const int rs = 3 * H * DH;
   LCI_CHECK(check_packed(qkv, rs) && check_packed(dqkv, rs) && check_packed(out, H * DH) &&
                 check_packed(dout, H * DH), "lci_attn_bwd: misaligned pointers");
-  // the placed kernels address q / k / v / dO rows through buffer resources with 32-bit sizes
-  LCI_CHECK((long long)(L + 4 * KT) * rs * 2 < (1ll << 31), "lci_attn_bwd: L=%d too long for 32-bit buffer offsets", L);
+  // the placed kernels address q / k / v / dO rows through buffer resources with 32-bit sizes; the dQ kernels stage
+  // key tiles up to two past the tile count padded to a multiple of 4: rows below L + 6 KT
+  LCI_CHECK((long long)(L + 6 * KT) * rs * 2 < (1ll << 31), "lci_attn_bwd: L=%d too long for 32-bit buffer offsets", L);
   LCI_CHECK(delta_ws != nullptr, "lci_attn_bwd: delta_ws (lci_attn_bwd_ws_bytes) is required");
   AttnArgs a{};
   const bf16* base = (const bf16*)qkv;
@@ -2169,10 +2630,24 @@ extern "C" int lci_attn_bwd_stage(int stage, const void* qkv, const void* out, c
     LCI_LAUNCH_CHECK();
   }
   if (stage < 0 || stage == 2) {
-    hipLaunchKernelGGL(attn_bwd_dq_hs_kernel, grid, dim3(HS_NW * 64), 0, s, a);
+    if (dq_variant < 0) dq_variant = lci_attn_bwd_dq_pick(B, L, H, attn_n_cu());
+    if (dq_variant == 1) {
+      // the wide kernel, then the narrow stream for the workgroups it flagged (none: a few microseconds)
+      hipLaunchKernelGGL(attn_bwd_dq_hs4_kernel, dim3((L + DQ4_QWG - 1) / DQ4_QWG, H, B), dim3(HS_NW * 64), 0, s, a);
+      LCI_LAUNCH_CHECK();
+      hipLaunchKernelGGL(attn_bwd_dq_hsfb_kernel, grid, dim3(HS_NW * 64), 0, s, a);
+    } else {
+      hipLaunchKernelGGL(attn_bwd_dq_hs_kernel, grid, dim3(HS_NW * 64), 0, s, a);
+    }
     LCI_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int lci_attn_bwd_stage(int stage, const void* qkv, const void* out, const void* dout, const float* lse2,
+                                  void* dqkv, float* delta_ws, int B, int L, int H, int head_dim, float scale,
+                                  void* stream) {
+  return lci_attn_bwd_variant(-1, stage, qkv, out, dout, lse2, dqkv, delta_ws, B, L, H, head_dim, scale, stream);
 }
 
 extern "C" int lci_attn_bwd(const void* qkv, const void* out, const void* dout, const float* lse2, void* dqkv,

@@ -107,6 +107,27 @@ def attn_bwd(qkv, out, dout, lse2, num_heads: int, scale: float):
     return dqkv
 
 
+def attn_bwd_variant(qkv, out, dout, lse2, num_heads: int, scale: float, dq_variant: int, stage: int = -1, ws=None,
+                     dqkv=None):
+    """attn_bwd with the dQ kernel forced (include/lci.h lci_attn_bwd_variant: 0 = 64 queries per wave, 1 = 128,
+    -1 = the library's pick); for tests and A/B timing. Returns (dqkv, flags): flags is the (B, H, ceil(L / 512)) int32
+    view of the workspace's per-workgroup flags, written only when the 128-query kernel ran. A single stage (0 = delta,
+    1 = dK/dV, 2 = dQ) needs the workspace `ws` of an earlier stage-0 call (an int32 tensor of
+    lci_attn_bwd_ws_bytes / 4 elements) and, to keep the other stages' results, its `dqkv`."""
+    _lib.require_gpu(qkv, out, dout, lse2)
+    B, L, C = qkv.shape
+    dh = C // (3 * num_heads)
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    if ws is None:
+        ws = torch.empty(int(_lib.load().lci_attn_bwd_ws_bytes(B, num_heads, L)) // 4, device=qkv.device,
+                         dtype=torch.int32)
+    _lib.call("lci_attn_bwd_variant", int(dq_variant), int(stage), qkv.data_ptr(), out.data_ptr(), dout.data_ptr(),
+              lse2.data_ptr(), dqkv.data_ptr(), ws.data_ptr(), B, L, num_heads, dh, float(scale), _lib.stream_of(qkv))
+    n0, nwg = B * num_heads * 2 * L, (L + 511) // 512
+    return dqkv, ws[n0:n0 + B * num_heads * nwg].view(B, num_heads, nwg)
+
+
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, num_heads, scale):

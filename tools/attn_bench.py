@@ -31,10 +31,31 @@ def main():
     ap.add_argument("--fwd-variant", type=int, nargs="+", choices=[0, 1], default=None,
                     help="time the forward alone with the kernel forced (0 = 64 queries per wave, 1 = 128); several "
                          "values alternate in one process, --rounds times each")
+    ap.add_argument("--dq-variant", type=int, nargs="+", choices=[0, 1], default=None,
+                    help="time the backward's dQ launch(es) alone with the kernel forced (0 = 64 queries per wave, "
+                         "1 = 128 + its fallback launch); several values alternate in one process, --rounds times each")
     ap.add_argument("--rounds", type=int, default=3)
     a = ap.parse_args()
     for L in a.L:
         qkv = torch.randn(a.B, L, 3 * a.H * 64, device="cuda").to(torch.bfloat16)
+        if a.dq_variant is not None:
+            f = 2.0 * a.B * a.H * L * L * 64
+            dout = torch.randn(a.B, L, a.H * 64, device="cuda").to(torch.bfloat16)
+            out, lse = kernels.attn_fwd(qkv, a.H, 0.125)
+            ws = torch.empty(kernels._lib.load().lci_attn_bwd_ws_bytes(a.B, a.H, L) // 4, device="cuda",
+                             dtype=torch.int32)
+            dqkv = torch.empty_like(qkv)
+            run = lambda v, stage: kernels.attn_bwd_variant(qkv, out, dout, lse, a.H, 0.125, v, stage, ws, dqkv)  # noqa: E731
+            run(0, 0)                 # the row constants, once
+            for v in a.dq_variant:    # warm both before the first timed round
+                _, flags = run(v, 2)
+            for rnd in range(a.rounds):
+                for v in a.dq_variant:
+                    t = timeit(lambda: run(v, 2), a.iters)
+                    print(json.dumps({"L": L, "B": a.B, "H": a.H, "round": rnd, "dq_variant": v, "dq_ms": round(t, 3),
+                                      "dq_tflops_alg": round(f / t / 1e9, 1),
+                                      "flagged": int(flags.sum().item()) if v == 1 else 0}), flush=True)
+            continue
         if a.fwd_variant is not None:
             f = 4.0 * a.B * a.H * L * L * 64
             for v in a.fwd_variant:   # warm both before the first timed round

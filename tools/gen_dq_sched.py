@@ -10,20 +10,30 @@ MFMA, M two gaps after the dP chain's last MFMA and in a later gap than its E, C
 2 exps and 4 VALU ops per gap; a block's pack of elements 0-7 (C 0-3) is complete one gap before its first dQ^T
 MFMA, elements 8-15 (C 4-7) one gap before its third. Output (stdout): the C++ table DQ_SCHED[24][4] of op codes
 (kind << 6 | block << 5 | index; 0xff = none); the placement is listed on stderr.
+
+With --nqb 4 (attn_bwd_dq_hs4_kernel: four query blocks per wave) the half has 48 gaps, block b's chains at gaps
+12b .. 12b+7 and the dQ^T MFMAs of block b-1 at 12b+8 .. 12b+11 (block 0's gaps: block 3 of the previous half); the
+same rules place every block's ops, and each block is done before the chains of block b+2 rewrite the S / dP / pack
+register set the two share. The table is DQ4_SCHED[48][4], block in bits 5:4 (index 0-15 in bits 3:0).
 """
+import argparse
 import sys
 
-NG = 24
-START_E = {0: 5, 1: 17}      # S chains at gaps 0-3 / 12-15
-START_M = {0: 9, 1: 21}      # dP chains at gaps 4-7 / 16-19
-DQ = {0: 20, 1: 8 + NG}      # first dQ^T gap that reads the block's packs
+ap = argparse.ArgumentParser()
+ap.add_argument("--nqb", type=int, default=2, choices=(2, 4),
+                help="query blocks of 32 per wave (2: attn_bwd_dq_hs_kernel, 4: attn_bwd_dq_hs4_kernel)")
+NQB = ap.parse_args().nqb
+NG = 12 * NQB
+START_E = {b: 12 * b + 5 for b in range(NQB)}    # S chains at gaps 12b .. 12b+3
+START_M = {b: 12 * b + 9 for b in range(NQB)}    # dP chains at gaps 12b+4 .. 12b+7
+DQ = {b: 12 * b + 20 for b in range(NQB)}        # first dQ^T gap that reads the block's packs (the last block's: next half)
 
 
 def main():
     cap_e = [0] * NG
     slots = [[] for _ in range(NG)]
     placed = {}
-    for qb in (1, 0):        # block 1 wraps into the next half: place it first
+    for qb in reversed(range(NQB)):   # the last block wraps into the next half: place it first
         tE, tM, tC = {}, {}, {}
         g = START_E[qb]
         while len(tC) < 8:
@@ -50,6 +60,8 @@ def main():
             assert g < START_E[qb] + 2 * NG, "does not fit"
         assert max(tC[j] for j in range(4)) < DQ[qb], (qb, tC)
         assert max(tC[j] for j in range(4, 8)) < DQ[qb] + 2, (qb, tC)
+        if NQB > 2:   # the block's register set is rewritten by the chains of block qb + 2
+            assert max(max(tE.values()), max(tM.values()), max(tC.values())) < 12 * qb + 24, (qb, tE, tM, tC)
         placed[qb] = (tE, tM, tC)
     code = {"E": 0, "M": 1, "C": 2}
     # Order within each gap (the periodic stream, gap 23 before gap 0): a conversion after the multiplies of its
@@ -85,9 +97,10 @@ def main():
     rows = []
     for g, s in enumerate(slots):
         print(f"// gap {g:2d}: " + " ".join(f"{k}{qb}.{i}" for k, qb, i in s), file=sys.stderr)
-        ops = [(code[k] << 6) | (qb << 5) | i for k, qb, i in s] + [0xFF] * (4 - len(s))
+        ops = [(code[k] << 6) | (qb << (5 if NQB == 2 else 4)) | i for k, qb, i in s] + [0xFF] * (4 - len(s))
         rows.append("{" + ", ".join(f"0x{o:02x}" for o in ops) + "}")
-    print("constexpr unsigned char DQ_SCHED[24][4] = {\n    " + ",\n    ".join(rows) + "};")
+    name = "DQ_SCHED" if NQB == 2 else f"DQ{NQB}_SCHED"
+    print(f"constexpr unsigned char {name}[{NG}][4] = {{\n    " + ",\n    ".join(rows) + "};")
 
 
 if __name__ == "__main__":

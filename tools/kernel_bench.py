@@ -48,12 +48,20 @@ def emit(name, ms, work, unit, cfg):
           flush=True)
 
 
-def bench_attention(fwd_variant=None):
+def bench_attention(fwd_variant=None, dq_variant=None):
     B, H, L = 2, 6, 65536
     qkv = torch.randn(B, L, 3 * H * 64, device="cuda").to(torch.bfloat16)
     dout = torch.randn(B, L, H * 64, device="cuda").to(torch.bfloat16)
     out, lse = kernels.attn_fwd(qkv, H, 0.125)
     f = 4.0 * B * H * L * L * 64
+    if dq_variant is not None:   # the dQ launch(es) alone with the kernel forced (0: 64 queries per wave, 1: 128)
+        ws = torch.empty(kernels._lib.load().lci_attn_bwd_ws_bytes(B, H, L) // 4, device="cuda", dtype=torch.int32)
+        dqkv = torch.empty_like(qkv)
+        kernels.attn_bwd_variant(qkv, out, dout, lse, H, 0.125, dq_variant, 0, ws, dqkv)   # the row constants
+        emit(f"attn_bwd_dq(variant {dq_variant})",
+             timeit(lambda: kernels.attn_bwd_variant(qkv, out, dout, lse, H, 0.125, dq_variant, 2, ws, dqkv)),
+             f / 2, "TFLOP/s", f"B{B} H{H} L{L} d64")
+        return
     if fwd_variant is not None:   # the forward alone with the kernel forced (0: 64 queries per wave, 1: 128)
         emit(f"attn_fwd(variant {fwd_variant})", timeit(lambda: kernels.attn_fwd_variant(qkv, H, 0.125, fwd_variant)),
              f, "TFLOP/s", f"B{B} H{H} L{L} d64")
@@ -409,9 +417,16 @@ def main():
         assert fwd_variant in (0, 1), "--fwd-variant takes 0 or 1"
         del argv[i:i + 2]
         argv = argv or ["attention"]
+    dq_variant = None
+    if "--dq-variant" in argv:   # --dq-variant {0,1}: the attention entry times that dQ kernel alone
+        i = argv.index("--dq-variant")
+        dq_variant = int(argv[i + 1])
+        assert dq_variant in (0, 1), "--dq-variant takes 0 or 1"
+        del argv[i:i + 2]
+        argv = argv or ["attention"]
     which = argv or ["attention", "window", "scan", "fftconv", "patch", "linear", "mlp"]
     if "attention" in which:
-        bench_attention(fwd_variant)
+        bench_attention(fwd_variant, dq_variant)
     if "window" in which:
         bench_window()
     if "wstages" in which:

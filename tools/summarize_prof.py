@@ -116,7 +116,9 @@ def main():
         for t, pat in TIMER_KERNELS.items():
             hits = [v for k, v in out.items() if re.search(pat, k)]
             if hits:
-                nl = sum(v["launches"] for v in hits)
+                # attn_bwd_dq_hsfb_kernel runs behind every attn_bwd_dq_hs4_kernel launch (one timer call = both):
+                # its bytes count, its launches are not calls of their own
+                nl = sum(v["launches"] for k, v in out.items() if re.search(pat, k) and "attn_bwd_dq_hsfb" not in k)
                 timers[t] = {"bytes_per_call": sum(v["launches"] * (v["read_bytes"] + v["write_bytes"]) for v in hits) / nl,
                              "kernels": sorted(k for k, v in out.items() if re.search(pat, k)), "launches": nl}
         path, wl = sys.argv[3], (sys.argv[4] if len(sys.argv) > 4 else "vit_p2_512")
