@@ -40,6 +40,11 @@
  *                         mamba.py:60-64,90, HyenaOperator in/out_proj hyena.py:278-279, Swin qkv/proj/mlp)
  *   lci_enhance_loss      Combined_Loss(["mse", "charbonnier", "gaussian3D"], [1, 1, 1]) (loss/loss_base.py:28-29,
  *                         loss/loss_functions/enhancement_losses.py:18-278) and its gradient
+ *   lci_enhance_metrics   torchmetrics' StructuralSimilarityIndexMeasure and PeakSignalNoiseRatio as the metric manager
+ *                         calls them per step for task_type=enhance (metrics/metrics_utils.py:21-26,
+ *                         metrics/metrics_base.py:167-180, 261-285)
+ *   lci_seg_f1            torch.argmax + torchmetrics' samplewise F1Score + torch.mean for task_type=seg
+ *                         (metrics/metrics_utils.py:19-20, metrics/metrics_base.py:162-180, 254-285)
  */
 #ifndef LCI_H_
 #define LCI_H_
@@ -63,8 +68,8 @@ extern "C" {
  * 31: lci_layernorm_bwd dres2; 32: one-chunk selective scan without end-state workspaces (xend / xinit / sdt null),
  * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes);
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
- * grows by the wide dQ kernel's per-workgroup flags. */
-#define LCI_ABI_VERSION 36
+ * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile. */
+#define LCI_ABI_VERSION 37
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -507,6 +512,39 @@ int lci_adam_step(float* const* p, const float* const* g, float* const* m, float
 long long lci_enhance_loss_ws_bytes(int B, int T, int H, int W);
 int lci_enhance_loss(const void* outputs, int out_dtype, const void* targets, int tgt_dtype, const float* taps,
                      void* grad, float* result, void* ws, int B, int T, int H, int W, void* stream);
+
+/* ------------------------------------------------------------------ task metrics (csrc/metrics.hip)
+ * The per-step metrics of the reference's metric manager, each left in device memory by one call: no host sync, no
+ * float atomics (bitwise reproducible), f32 arithmetic with f64 final sums whatever the input dtype.
+ *
+ * lci_enhance_metrics: outputs p, targets t (B, C, T, H, W) contiguous, each f32 or bf16 (dtype codes above);
+ * result[2] f32 = {ssim, psnr}. T == 1 is the 2-D case (the reference slices [:, :, 0]): the windowed axes are H, W;
+ * otherwise T, H, W. Every windowed extent must be at least 11.
+ *   ssim: window g[j] = exp(-((j - 5) / 1.5)^2 / 2), j = 0..10, normalised, outer product over the windowed axes;
+ *     R = max(max p - min p, max t - min t) over the whole batch, c1 = (0.01 R)^2, c2 = (0.03 R)^2; with E[.] the
+ *     windowed mean, mu_p = E[p], mu_t = E[t], var_p = max(E[p^2] - mu_p^2, 0), var_t likewise, cov = E[pt] - mu_p mu_t,
+ *     s = (2 mu_p mu_t + c1)(2 cov + c2) / ((mu_p^2 + mu_t^2 + c1)(var_p + var_t + c2)) at every (b, c) and every
+ *     interior voxel (index in [5, n - 6] on each windowed axis); ssim = the mean of s (torchmetrics reflect-pads by 5,
+ *     convolves 'valid' and crops 5 again: the same values).
+ *   psnr = 10 log10(R'^2 / (sum (p - t)^2 / N)), R' = max(max t, 0) - min(min t, 0), N = B C T H W; +inf for p == t.
+ *   A NaN input makes both NaN. ws: lci_enhance_metrics_ws_bytes(B, C, T, H, W) bytes (-1 for a bad shape), 16-byte
+ *   aligned, written and read by the call.
+ * lci_ssim_tile(axis): the interior extents one workgroup covers along T (3-D only), H, W for axis 0, 1, 2.
+ *
+ * lci_seg_f1: logits (B, C, S) contiguous f32 or bf16, 2 <= C <= 64, S < 2^31; labels (B, S) int64.
+ *   pred = the first index of the maximum over C (torch.argmax); counts (B, C, 3) int64 = tp, fp, fn per sample and
+ *   class; a label outside [0, C) matches no class (it counts as fp of pred only) and is not reported.
+ *   Per sample, C == 2 (the reference's 'binary' task): 2 tp / (2 tp + fp + fn) of class 1, 0 for a zero denominator;
+ *   C > 2: the mean of the per-class 2 tp / (2 tp + fp + fn) over the classes with tp + fp + fn > 0.
+ *   result[1] f32 = the mean over the samples. ws: lci_seg_f1_ws_bytes(B, C, S) bytes (-1 for a bad shape), 16-byte
+ *   aligned. */
+int lci_ssim_tile(int axis);
+long long lci_enhance_metrics_ws_bytes(int B, int C, int T, int H, int W);
+int lci_enhance_metrics(const void* outputs, int out_dtype, const void* targets, int tgt_dtype, float* result,
+                        void* ws, int B, int C, int T, int H, int W, void* stream);
+long long lci_seg_f1_ws_bytes(int B, int C, long long S);
+int lci_seg_f1(const void* logits, int dtype, const long long* labels, long long* counts, float* result, void* ws,
+               int B, int C, long long S, void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "liblci.so")
 LIB_PATH = os.environ.get("LCI_LIB_PATH", DEFAULT_LIB)   # override: kernel-variant A/B runs (no staleness check)
-ABI_VERSION = 36  # include/lci.h LCI_ABI_VERSION
+ABI_VERSION = 37  # include/lci.h LCI_ABI_VERSION
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -93,6 +93,8 @@ SIGNATURES = {
     "lci_adam_step": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _I, _P],
     "lci_hyena_filter_bwd": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "lci_enhance_loss": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "lci_enhance_metrics": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "lci_seg_f1": [_P, _I, _P, _P, _P, _P, _I, _I, _L, _P],
 }
 
 _lib = None
@@ -173,6 +175,12 @@ def load(path: str = LIB_PATH):
     lib.lci_direct_conv_dk_splits.argtypes = [_I, _I, _I]
     lib.lci_enhance_loss_ws_bytes.restype = ctypes.c_longlong
     lib.lci_enhance_loss_ws_bytes.argtypes = [_I, _I, _I, _I]
+    lib.lci_enhance_metrics_ws_bytes.restype = ctypes.c_longlong
+    lib.lci_enhance_metrics_ws_bytes.argtypes = [_I, _I, _I, _I, _I]
+    lib.lci_seg_f1_ws_bytes.restype = ctypes.c_longlong
+    lib.lci_seg_f1_ws_bytes.argtypes = [_I, _I, _L]
+    lib.lci_ssim_tile.restype = ctypes.c_int
+    lib.lci_ssim_tile.argtypes = [_I]
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -186,6 +194,14 @@ def call(name: str, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise LciError(f"{name} failed (rc={rc}): {lib.lci_last_error().decode()}")
+
+
+def plain_tensors():
+    """Context for building a cached constant tensor. Under torch.inference_mode() (trainer.EvalStep) it leaves that
+    mode, so the tensor is a plain one that a later training step may save for its backward; anywhere else it does
+    nothing at all (torch.inference_mode(False) would also switch grad mode on inside a no_grad region)."""
+    import contextlib
+    return torch.inference_mode(False) if torch.is_inference_mode_enabled() else contextlib.nullcontext()
 
 
 def stream_of(t: torch.Tensor) -> int:

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import kernels
+from . import _lib, kernels
 
 
 def ensure_tuple_rep(tup, dim):
@@ -82,7 +82,8 @@ def layer_norm_no_affine(x: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     key = (x.shape[-1], x.device)
     wb = _UNIT_AFFINE.get(key)
     if wb is None:
-        wb = (torch.ones(x.shape[-1], device=x.device), torch.zeros(x.shape[-1], device=x.device))
+        with _lib.plain_tensors():   # plain tensors even when first built in an EvalStep: training reuses them
+            wb = (torch.ones(x.shape[-1], device=x.device), torch.zeros(x.shape[-1], device=x.device))
         _UNIT_AFFINE[key] = wb
     return kernels.layer_norm(x, wb[0], wb[1], eps, False)
 

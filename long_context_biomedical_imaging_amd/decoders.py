@@ -21,7 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import kernels
+from . import _lib, kernels
 
 # A/B switch for the 2-D heads (the headline ViTUNETR at 512^2): HIP conv3 + inorm (default; same step time as
 # MIOpen at 512^2, without its ~2 min first-call solver search) vs torch/MIOpen (LCI_HIP_CONV_2D=0)
@@ -584,7 +584,8 @@ def _lin_interp_matrix(out_size, in_size, device):
         rows = torch.arange(out_size)
         m.index_put_((rows, i0), 1.0 - lam1, accumulate=True)
         m.index_put_((rows, i1), lam1, accumulate=True)
-        m = m.to(device)
+        with _lib.plain_tensors():   # a plain tensor even when first built in an EvalStep: training reuses it
+            m = m.to(device).clone()
         _SEP_CACHE[key] = m
     return m
 
@@ -598,7 +599,8 @@ def _avg_pool_matrix(out_size, in_size, device):
         for i in range(out_size):
             a, b = (i * in_size) // out_size, -((-(i + 1) * in_size) // out_size)
             m[i, a:b] = 1.0 / (b - a)
-        m = m.to(device)
+        with _lib.plain_tensors():   # as in _lin_interp_matrix
+            m = m.to(device).clone()
         _SEP_CACHE[key] = m
     return m
 

@@ -527,7 +527,8 @@ def _mp_slot_rows(ks2, device):
             st, k = sl // 16, sl % 16
             h, j = k >> 3, k & 7
             rows.append(32 * (st >> 1) + 16 * (st & 1) + (j & 3) + 8 * (j >> 2) + 4 * h)
-        t = torch.tensor(rows, device=device)
+        with _lib.plain_tensors():   # a plain tensor even when first built in an EvalStep: training reuses it
+            t = torch.tensor(rows, device=device)
         _MP_IDX[key] = t
     return t
 
@@ -844,7 +845,8 @@ def _twiddles(n, device):
     key = (n, str(device))
     t = _TW.get(key)
     if t is None:
-        t = torch.empty(n, 2, device=device, dtype=torch.float32)
+        with _lib.plain_tensors():   # as in _mp_slot_rows
+            t = torch.empty(n, 2, device=device, dtype=torch.float32)
         _lib.call("lci_fft_twiddles", t.data_ptr(), n, _lib.stream_of(t))
         _TW[key] = t
     return t
@@ -1089,7 +1091,8 @@ def _hf_inv(device):
     """inv[f] = permuted column holding feature f."""
     inv = _HF_INV.get(str(device))
     if inv is None:
-        inv = torch.argsort(_hf_feature_of_column()).to(device)
+        with _lib.plain_tensors():   # as in _mp_slot_rows
+            inv = torch.argsort(_hf_feature_of_column()).to(device)
         _HF_INV[str(device)] = inv
     return inv
 
@@ -2365,3 +2368,74 @@ def enhance_loss(outputs: torch.Tensor, targets: torch.Tensor, taps: torch.Tenso
     if outputs.numel() == 0:
         raise _lib.LciError("enhance_loss: empty tensors")
     return _EnhanceLoss.apply(outputs, targets, taps)
+
+
+# ------------------------------------------------------------------------------------------- task metrics
+SSIM_TILE = (6, 16, 32)   # interior (T, H, W) extents one workgroup of csrc/metrics.hip covers (lci_ssim_tile); 2-D: H, W
+_METRIC_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
+
+
+def enhance_metrics(outputs: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
+    """torchmetrics' SSIM and PSNR as the reference's metric manager calls them per step for task_type=enhance
+    (metrics/metrics_base.py:167-180; data_range=None, gaussian 11-tap window, sigma 1.5) of (B, C, T, H, W) f32 / bf16
+    CUDA tensors on csrc/metrics.hip: a detached (2,) f32 tensor (ssim, psnr) on the device, no host sync. T == 1 is
+    the 2-D case (windowed over H, W), otherwise the window runs over T, H, W; a windowed extent below 11 has no
+    interior voxel and raises ValueError (include/lci.h states the formulas)."""
+    if outputs.dim() != 5 or outputs.shape != targets.shape:
+        raise ValueError(f"enhance_metrics: outputs {tuple(outputs.shape)} and targets {tuple(targets.shape)} must "
+                         "be the same (B, C, T, H, W) shape")
+    for t in (outputs, targets):
+        if t.dtype not in _METRIC_DTYPES:
+            raise ValueError(f"enhance_metrics: dtype {t.dtype} (f32 or bf16 only)")
+    B, C, T, H, W = outputs.shape
+    if min(B, C, T) < 1:
+        raise ValueError(f"enhance_metrics: empty tensors {tuple(outputs.shape)}")
+    windowed = {"H": H, "W": W} if T == 1 else {"T": T, "H": H, "W": W}
+    short = {k: v for k, v in windowed.items() if v < 11}
+    if short:
+        raise ValueError(f"enhance_metrics: windowed extent(s) {short} below the 11-tap SSIM window: no interior "
+                         "voxel to average over")
+    outputs, targets = outputs.detach().contiguous(), targets.detach().contiguous()
+    _lib.require_gpu(outputs, targets)
+    lib = _lib.load()
+    ws = torch.empty(lib.lci_enhance_metrics_ws_bytes(B, C, T, H, W), device=outputs.device, dtype=torch.uint8)
+    res = torch.empty(2, device=outputs.device, dtype=torch.float32)
+    # both tensors are read by the statistics pass and again by the window pass
+    traffic = float(2 * outputs.numel() * (outputs.element_size() + targets.element_size()))
+    KernelTimer.run("enhance_metrics", traffic, outputs, lambda: _lib.call(
+        "lci_enhance_metrics", outputs.data_ptr(), _METRIC_DTYPES[outputs.dtype], targets.data_ptr(),
+        _METRIC_DTYPES[targets.dtype], res.data_ptr(), ws.data_ptr(), B, C, T, H, W, _lib.stream_of(outputs)))
+    return res
+
+
+def seg_f1(logits: torch.Tensor, labels: torch.Tensor):
+    """torch.argmax over the channels + torchmetrics' samplewise F1 + the mean over the samples, the reference's
+    per-step metric for task_type=seg (metrics/metrics_base.py:162-180), on csrc/metrics.hip. logits (B, C, *spatial)
+    f32 / bf16 with 2 <= C <= 64, labels (B, *spatial) int64. Returns (f1, counts): the f32 scalar and the int64
+    (B, C, 3) tp / fp / fn per sample and class, both on the device, no host sync. C == 2 scores class 1 ('binary');
+    C > 2 is the macro mean over the classes that occur in the sample's prediction or labels."""
+    if logits.dim() < 3 or labels.dim() != logits.dim() - 1 or \
+            (logits.shape[0], *logits.shape[2:]) != tuple(labels.shape):
+        raise ValueError(f"seg_f1: logits {tuple(logits.shape)} must be (B, C, *spatial) and labels "
+                         f"{tuple(labels.shape)} (B, *spatial)")
+    B, C = logits.shape[:2]
+    if not 2 <= C <= 64:
+        raise ValueError(f"seg_f1: C = {C} outside [2, 64]")
+    if logits.dtype not in _METRIC_DTYPES:
+        raise ValueError(f"seg_f1: logits dtype {logits.dtype} (f32 or bf16 only)")
+    if labels.dtype != torch.int64:
+        raise ValueError(f"seg_f1: labels dtype {labels.dtype} (int64 only)")
+    S = labels[0].numel() if B else 0
+    if B < 1 or S < 1 or S >= 2 ** 31:
+        raise ValueError(f"seg_f1: B = {B}, {S} positions per sample (1 .. 2^31 - 1)")
+    logits, labels = logits.detach().contiguous(), labels.contiguous()
+    _lib.require_gpu(logits, labels)
+    lib = _lib.load()
+    ws = torch.empty(lib.lci_seg_f1_ws_bytes(B, C, S), device=logits.device, dtype=torch.uint8)
+    counts = torch.empty(B, C, 3, device=logits.device, dtype=torch.int64)
+    res = torch.empty(1, device=logits.device, dtype=torch.float32)
+    traffic = float(logits.numel() * logits.element_size() + labels.numel() * 8)
+    KernelTimer.run("seg_f1", traffic, logits, lambda: _lib.call(
+        "lci_seg_f1", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), counts.data_ptr(),
+        res.data_ptr(), ws.data_ptr(), B, C, S, _lib.stream_of(logits)))
+    return res[0], counts

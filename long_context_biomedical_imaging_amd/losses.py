@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import kernels
+from . import _lib, kernels
 
 # Combined_Loss's GaussianDeriv3D_Loss(sigmas=[0.25, 0.5, 1.0], sigmas_T=[0.25, 0.5, 0.5]) (enhancement_losses.py:264)
 SIGMAS = (0.25, 0.5, 1.0)       # along H and W
@@ -61,7 +61,8 @@ def enhance_taps(device) -> torch.Tensor:
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     if device not in _taps_cache:
-        _taps_cache[device] = enhance_taps_host().to(device)
+        with _lib.plain_tensors():   # a plain tensor even when first built in an EvalStep: training reuses it
+            _taps_cache[device] = enhance_taps_host().to(device)
     return _taps_cache[device]
 
 
@@ -90,6 +91,7 @@ class CombinationEnhanceLoss:
             raise NotImplementedError("CombinationEnhanceLoss: per-sample weights are not implemented")
         taps = self._taps.get(outputs.device)
         if taps is None:
-            taps = self._taps[outputs.device] = self.taps_host.to(outputs.device)
+            with _lib.plain_tensors():   # as in enhance_taps
+                taps = self._taps[outputs.device] = self.taps_host.to(outputs.device)
         loss, self.components = kernels.enhance_loss(outputs, targets, taps)
         return loss

@@ -175,6 +175,8 @@ class TrainStep:
         self.accum = max(1, int(getattr(config, "iters_to_accumulate", 1) or 1))
         self.micro = 0   # micro-batches since the last optimizer step (trainer_base.py:172 `idx`)
         self.dup_batch1 = any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules())
+        # opt-in: a metrics.TaskMetrics scored on every step (trainer_base.py:186 on_train_step_end), on the device
+        self.metrics = None
         self.optim.zero_grad(set_to_none=True)
 
     def step(self, inputs, targets, update: bool | None = None):
@@ -191,6 +193,8 @@ class TrainStep:
             out = self.model(inputs)
             loss = self.loss_func(out, targets) / self.accum
         loss.backward()
+        if self.metrics is not None:
+            self.metrics.update(loss.detach() * self.accum, out.detach(), targets)
         self.micro += 1
         if update is None:
             update = self.micro % self.accum == 0
@@ -268,6 +272,41 @@ class GraphedStep:
         return self.loss
 
 
+class EvalStep:
+    """The reference's evaluation step (trainer_base.py:292-315): step(inputs, targets) runs the model in eval()
+    under torch.inference_mode() and the trainer's bf16 autocast, computes the configured loss and scores the batch
+    into `self.metrics` (a metrics.TaskMetrics, sums kept on the device). Returns (output, loss), both device
+    tensors: no host sync per step; `metrics.result()` is the one sync of an evaluation loop. Every module's training
+    flag is restored afterwards, so a step can be interleaved with training.
+
+    Deviation: a batch of 1 is not duplicated. The reference repeats it and slices the output back
+    (trainer_base.py:305-311) "so batch norm doesn't throw an error", but in eval mode BatchNorm normalises with its
+    running statistics, which neither fails on one sample nor depends on the batch: the duplicate only doubles the
+    work."""
+
+    def __init__(self, model, config, device):
+        from .metrics import TaskMetrics
+        self.device = device
+        self.model = model
+        self.loss_func = loss_fn(config)
+        self.use_amp = bool(config.use_amp)
+        self.metrics = TaskMetrics(config)
+
+    def step(self, inputs, targets):
+        flags = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+        dev = "cuda" if self.device.type == "cuda" else "cpu"
+        try:
+            with torch.inference_mode(), torch.autocast(device_type=dev, dtype=torch.bfloat16, enabled=self.use_amp):
+                out = self.model(inputs)
+                loss = self.loss_func(out, targets)
+                self.metrics.update(loss, out, targets)
+        finally:
+            for m, flag in flags:
+                m.training = flag
+        return out, loss
+
+
 def synthetic_batch(config, batch, device, seed):
     """U[0,1) images (B, C, T, H, W) and targets of the task's shape."""
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -281,4 +320,4 @@ def synthetic_batch(config, batch, device, seed):
     return x.to(device), y.to(device)
 
 
-__all__ = ["init_distributed", "TrainStep", "synthetic_batch", "LciAdam", "LciAdamW", "F"]
+__all__ = ["init_distributed", "TrainStep", "EvalStep", "synthetic_batch", "LciAdam", "LciAdamW", "F"]
