@@ -56,7 +56,7 @@ struct WinArgs {
   bf16* out; const bf16* o; const bf16* dout;
   float* lse2;                             // (Bw, H, N)
   bf16* dqkv; float* dbias_pad;            // bwd
-  float* pad_ws;                           // bwd1: (Bw, H, 64) per-workgroup pad-key dK | dV sums, or null
+  float* pad_ws;                           // bwd: (Bw, H, 64) per-workgroup pad-key dK | dV sums, or null
   bf16* dS;                                // (Bw, H, nqb, nkt, 64, 16) bf16 tiles or null
   float* drpb;                             // (H, N, N) f32 (reduction kernel)
   int mode, nd, S[3], ws[3], sh[3], Sp[3], nwin[3];
@@ -518,6 +518,9 @@ __global__ __launch_bounds__(NW * 64) void win_attn_bwd_kernel(WinArgs a) {
 
   // ---------------- phase 2: Q, dO in LDS; key on the lane -> dK, dV
   win_stage<NW * 64>(a, L, hh * WHD, hh * WHD, true, a.dout, w);   // Q -> t0, dO -> t1
+  float padsum_k[16], padsum_v[16];   // this lane's padded keys' dK | dV (-> the qkv bias gradient)
+#pragma unroll
+  for (int i = 0; i < 16; ++i) padsum_k[i] = padsum_v[i] = 0.f;
   for (int kb = wave; kb < a.nqb; kb += NW) {
     const int key = kb * 32 + (lane & 31);
     const bool kv = key < a.N;
@@ -575,25 +578,42 @@ __global__ __launch_bounds__(NW * 64) void win_attn_bwd_kernel(WinArgs a) {
         }
       }
     }
-    // padded voxels: their k, v are the qkv bias. All padded keys of the wave target the same 2 x 32 words,
-    // so sum over the 32 key lanes of each half first (one atomic per word per wave instead of one per key:
-    // per-key atomics serialised on 192 addresses cost ~37 ms at Swin-tiny stage 1, 128^3)
+    // padded voxels: their k, v are the qkv bias. Every padded key of the workgroup adds into the same 2 x 32 words:
+    // the lanes keep their own sums over this wave's key blocks; they are reduced once, below
     const bool padk = kv && krow < 0 && a.dbias_pad != nullptr;
     if (__any(padk)) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        float sk = padk ? dk[i] * a.scale : 0.f, sv = padk ? dv[i] : 0.f;
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) {
-          sk += __shfl_xor(sk, o);
-          sv += __shfl_xor(sv, o);
-        }
-        if ((lane & 31) == 0) {
-          const int d = 8 * (i >> 2) + 4 * half + (i & 3);
-          atomicAdd(a.dbias_pad + a.C + hh * WHD + d, sk);
-          atomicAdd(a.dbias_pad + 2 * a.C + hh * WHD + d, sv);
-        }
+        padsum_k[i] += padk ? dk[i] * a.scale : 0.f;
+        padsum_v[i] += padk ? dv[i] : 0.f;
       }
+    }
+  }
+  // One (k | v) x 32 partial per workgroup into pad_ws, summed over windows by win_pad_reduce_kernel, as in the
+  // single-phase kernel: lanes in a fixed shuffle tree, then the waves in wave order through LDS (the staged tiles
+  // are dead). Deterministic -- float atomics onto dbias_pad from every boundary window were not.
+  if (a.pad_ws != nullptr) {
+    __syncthreads();   // every wave is done with t0 / t1
+    float* pw = (float*)L.t0 + wave * 64;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      float sk = padsum_k[i], sv = padsum_v[i];
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) {
+        sk += __shfl_xor(sk, o);
+        sv += __shfl_xor(sv, o);
+      }
+      if ((lane & 31) == 0) {
+        const int d = 8 * (i >> 2) + 4 * half + (i & 3);
+        pw[d] = sk;
+        pw[32 + d] = sv;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+      float acc = 0.f;
+      for (int v = 0; v < NW; ++v) acc += ((const float*)L.t0)[v * 64 + threadIdx.x];
+      a.pad_ws[((long long)w * a.H + hh) * 64 + threadIdx.x] = acc;
     }
   }
 }
@@ -1129,6 +1149,7 @@ extern "C" int lci_window_attn_bwd(const void* qkv, const float* qkv_bias, const
   const int bwd1_env = win_bwd1_enabled();
   static const int nw_env = getenv("LCI_WIN_BWD_WAVES") ? atoi(getenv("LCI_WIN_BWD_WAVES")) : 4;
   LCI_CHECK(biasT && ((uintptr_t)biasT & 15) == 0, "window_attn_bwd: biasT must be a 16-byte aligned table");
+  a.pad_ws = dbias_pad ? pad_ws : nullptr;   // per-workgroup pad-key partials, reduced after the attention kernel
   if (bwd1_env && a.nkt <= WBWD1_MAXW) {
     a.dS_kl = 1;
     static const int cnt_env = getenv("LCI_WIN_BWD1_CNT") ? atoi(getenv("LCI_WIN_BWD1_CNT")) : 1;
@@ -1138,10 +1159,7 @@ extern "C" int lci_window_attn_bwd(const void* qkv, const float* qkv_bias, const
     LCI_CHECK(lds <= 160 * 1024, "window_attn_bwd: %zu B of LDS", lds);
     (void)hipFuncSetAttribute((const void*)win_attn_bwd1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
-    a.pad_ws = dbias_pad ? pad_ws : nullptr;
     hipLaunchKernelGGL(win_attn_bwd1_kernel, dim3(a.Bw * a.H), dim3(a.nkt * 64), lds, s, a);
-    LCI_LAUNCH_CHECK();
-    if (dbias_pad) hipLaunchKernelGGL(win_pad_reduce_kernel, dim3(a.H * 64), dim3(256), 0, s, a);
   } else if (!bias) {
     LCI_CHECK(false, "window_attn_bwd: the two-phase kernel (N > %d or LCI_WIN_BWD1=0) needs the plain table too",
               WBWD1_MAXW * 32);
@@ -1155,6 +1173,10 @@ extern "C" int lci_window_attn_bwd(const void* qkv, const float* qkv_bias, const
     hipLaunchKernelGGL(win_attn_bwd_kernel<4>, dim3(a.Bw * a.H), dim3(256), win_lds(a, true), s, a);
   }
   LCI_LAUNCH_CHECK();
+  if (dbias_pad) {
+    hipLaunchKernelGGL(win_pad_reduce_kernel, dim3(a.H * 64), dim3(256), 0, s, a);
+    LCI_LAUNCH_CHECK();
+  }
   if (dS && drpb) {
     const long long per_w = (long long)a.H * a.nqb * a.nkt * 1024;
     hipLaunchKernelGGL(win_rpb_grad_kernel, dim3((unsigned)((per_w / 8 + 127) / 128)), dim3(128), 0, s, a);

@@ -151,3 +151,56 @@ def swin_part1(x, ln_w, ln_b, ws_cfg, ss_cfg, attn_fn, mask_matrix):
 
 def padded_dims(dims, ws):
     return [int(np.ceil(d / w)) * w for d, w in zip(dims, ws)]
+
+
+def window_attention_windows(qkv, rpb, mask, num_heads, scale):
+    """The window-attention op on pre-partitioned windows, at the kernel boundary (no LN, no Linear).
+
+    qkv (Bw, N, 3C) with channels [q | k | v] x (heads, head_dim); rpb (H, N, N); mask (nW, N, N) or None.
+    Returns out (Bw, N, C) and lse2 (Bw, H, N), the log2-domain log-sum-exp of the logits (detached)."""
+    bw, n, c3 = qkv.shape
+    t = qkv.reshape(bw, n, 3, num_heads, c3 // (3 * num_heads)).permute(2, 0, 3, 1, 4)
+    q, k, v = t[0], t[1], t[2]
+    out = window_attention_core(q, k, v, rpb, mask, scale)
+    with torch.no_grad():
+        logits = (q * scale) @ k.transpose(-2, -1) + rpb.unsqueeze(0)
+        if mask is not None:
+            nw = mask.shape[0]
+            logits = (logits.view(bw // nw, nw, num_heads, n, n) + mask.unsqueeze(1).unsqueeze(0)).view_as(logits)
+        lse2 = torch.logsumexp(logits, -1) / np.log(2.0)
+    return out.transpose(1, 2).reshape(bw, n, c3 // 3), lse2
+
+
+def grid_to_windows(x, fill, ws, ss):
+    """(B, *S, c) -> (B * nW, N, c): pad to a multiple of the window with rows equal to `fill` (c,), roll by -shift,
+    window_partition. Also returns the padded dims [B, *Sp]. ws / ss as get_window_size resolved them."""
+    S = list(x.shape[1:-1])
+    sp = padded_dims(S, ws)
+    pad = []
+    for s, p in zip(reversed(S), reversed(sp)):
+        pad += [0, p - s]
+    real = F.pad(torch.ones(1, *S, 1, dtype=x.dtype, device=x.device), [0, 0] + pad)
+    x = F.pad(x, [0, 0] + pad) + (1 - real) * fill
+    if any(s > 0 for s in ss):
+        x = torch.roll(x, shifts=tuple(-s for s in ss), dims=tuple(range(1, 1 + len(S))))
+    return window_partition(x, ws), [x.shape[0], *sp]
+
+
+def windows_to_grid(win, ws, ss, dims, S):
+    """(B * nW, N, c) -> (B, *S, c): window_reverse, roll by +shift, crop."""
+    x = window_reverse(win.reshape(-1, *ws, win.shape[-1]), ws, dims)
+    if any(s > 0 for s in ss):
+        x = torch.roll(x, shifts=tuple(ss), dims=tuple(range(1, 1 + len(S))))
+    return x[(slice(None),) + tuple(slice(0, s) for s in S)].contiguous()
+
+
+def window_attention_grid(qkv, bias, rpb, ws, ss, num_heads, scale):
+    """What the fused grid-mode op computes, at the kernel boundary: channels-last qkv (B, *S, 3C), the qkv bias
+    (3C) as the value of padded voxels (None: zeros), rpb (H, N, N); ws / ss as get_window_size resolved them.
+    Returns out (B, *S, C) and lse2 (B * nW, H, N) in the log2 domain (detached). Differentiable in qkv, bias, rpb."""
+    S = list(qkv.shape[1:-1])
+    fill = bias if bias is not None else torch.zeros(qkv.shape[-1], dtype=qkv.dtype, device=qkv.device)
+    win, dims = grid_to_windows(qkv, fill, ws, ss)
+    mask = compute_mask(dims[1:], ws, ss).to(qkv) if any(s > 0 for s in ss) else None
+    out, lse2 = window_attention_windows(win, rpb, mask, num_heads, scale)
+    return windows_to_grid(out, ws, ss, dims, S), lse2

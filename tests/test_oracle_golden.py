@@ -154,6 +154,55 @@ def test_window_attention(name, ws):
     assert_close(rpb.grad, g.t("grad/relative_position_bias_table"), 1e-4, 1e-5, "window attn drpb")
 
 
+@pytest.mark.parametrize("dims,ws_cfg,ss_cfg", [((10, 9, 5), (4, 4, 4), (2, 2, 2)),   # padded on every axis, shifted
+                                                ((9, 6), (4, 4), (2, 2))])
+def test_window_attention_grid_matches_part1_path(dims, ws_cfg, ss_cfg):
+    """The kernel-level reference (window.window_attention_grid: no LN, no Linear) against the golden-pinned path,
+    swin_part1 around window_attention with an identity projection, in fp64: same output, same gradients. The
+    kernel-level d(qkv) enters through the gradients of x and of the qkv weight."""
+    C, H, B = 8, 2, 2
+    g = torch.Generator().manual_seed(5)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)   # noqa: E731
+    ws, ss = window.get_window_size(dims, ws_cfg, ss_cfg)
+    n = int(np.prod(ws))
+    idx = window.relative_position_index(ws)
+    ln_w, ln_b = torch.ones(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64)
+    x0, w0, b0, t0 = r(B, *dims, C), r(3 * C, C) * 0.5, r(3 * C) * 0.5, r(int(idx.max()) + 1, H) * 0.5
+    cot = r(B, *dims, C)
+    mask = window.compute_mask(window.padded_dims(dims, ws), ws, ss).double()
+
+    def leaves():
+        return [t.clone().requires_grad_(True) for t in (x0, w0, b0, t0)]
+
+    x, w, b, t = leaves()
+    ref = window.swin_part1(x, ln_w, ln_b, ws_cfg, ss_cfg, lambda win, m: window.window_attention(
+        win, m, w, b, torch.eye(C, dtype=torch.float64), torch.zeros(C, dtype=torch.float64), t, idx, H), mask)
+    (ref * cot).sum().backward()
+    x2, w2, b2, t2 = leaves()
+    qkv = torch.nn.functional.linear(torch.nn.functional.layer_norm(x2, (C,), ln_w, ln_b), w2, b2)
+    rpb = t2[torch.as_tensor(idx).reshape(-1)].reshape(n, n, H).permute(2, 0, 1)
+    out, lse2 = window.window_attention_grid(qkv, b2, rpb, ws, ss, H, (C // H) ** -0.5)
+    (out * cot).sum().backward()
+    assert lse2.shape == (B * int(np.prod([p // a for p, a in zip(window.padded_dims(dims, ws), ws)])), H, n)
+    # golden_util.assert_close compares in float32; fp64 round-off needs the comparison in fp64
+    def close64(a, e, what):
+        assert a.dtype == e.dtype == torch.float64 and a.shape == e.shape, what
+        assert bool(((a - e).abs() <= 1e-10 + 1e-10 * e.abs()).all()), f"{what}: max err {(a - e).abs().max():.3e}"
+
+    close64(out.detach(), ref.detach(), "out")
+    for name, a, e in (("dx", x2, x), ("d(qkv weight)", w2, w), ("d(qkv bias)", b2, b), ("d(table)", t2, t)):
+        close64(a.grad, e.grad, name)
+    # lse2 is the log2 of the softmax denominator: the weights rebuilt from it sum to one in every row
+    win, _ = window.grid_to_windows(qkv.detach(), b0, ws, ss)
+    hd = C // H
+    q = win[..., :C].reshape(-1, n, H, hd).transpose(1, 2) * hd ** -0.5
+    k = win[..., C:2 * C].reshape(-1, n, H, hd).transpose(1, 2)
+    logits = q @ k.transpose(-2, -1) + rpb.detach()
+    logits = (logits.view(B, -1, H, n, n) + mask[None, :, None]).view(-1, H, n, n)
+    psum = torch.exp(logits - lse2.unsqueeze(-1) * np.log(2.0)).sum(-1)
+    close64(psum, torch.ones_like(psum), "lse2")
+
+
 def test_swin_index_ops_bit_exact():
     g = Golden("swin_index")
     assert np.array_equal(g.z["out/rp_index_3d"], window.relative_position_index((7, 7, 7)))

@@ -37,6 +37,8 @@ def _oracle_part1(blk, x, ws_cfg, ss_cfg):
     sd = {k: (v.detach().double() if v.is_floating_point() else v).cpu() for k, v in blk.state_dict().items()}
     sd["attn.qkv.bias"].requires_grad_(True)   # the padded voxels' k / v are this bias: its gradient is checked
     _oracle_part1.qkv_bias = sd["attn.qkv.bias"]
+    sd["attn.relative_position_bias_table"].requires_grad_(True)
+    _oracle_part1.rpb_table = sd["attn.relative_position_bias_table"]
 
     def attn_fn(win, mask):
         return ow.window_attention(win, mask, sd["attn.qkv.weight"], sd["attn.qkv.bias"], sd["attn.proj.weight"],
@@ -80,6 +82,7 @@ def test_swin_part1_grid_vs_oracle(dims, ws, shift, C, heads):
     ref.backward(cot.double())
     assert rel_err(xc.grad, xr.grad) < 5e-2, "dx"
     assert rel_err(blk.attn.qkv.bias.grad, _oracle_part1.qkv_bias.grad) < 5e-2, "d(qkv bias), incl. padded voxels"
+    assert rel_err(blk.attn.relative_position_bias_table.grad, _oracle_part1.rpb_table.grad) < 5e-2, "d(rpb table)"
 
 
 def test_swin_basic_layer_vs_reference():
