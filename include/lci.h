@@ -45,6 +45,10 @@
  *                         metrics/metrics_base.py:167-180, 261-285)
  *   lci_seg_f1            torch.argmax + torchmetrics' samplewise F1Score + torch.mean for task_type=seg
  *                         (metrics/metrics_utils.py:19-20, metrics/metrics_base.py:162-180, 254-285)
+ *   lci_adam_step(_ex)    optimizer.step() of Adam / AdamW (trainer/trainer_base.py:171-177, optim/optim_base.py:87-89);
+ *                         _ex also evaluates the recipes' OneCycleLR (optim_base.py:113-115, stepped at
+ *                         trainer_base.py:181-182) from the device step count, or reads a device learning rate
+ *   lci_grad_sumsq/_clip_coef  nn.utils.clip_grad_norm_'s norm and coefficient (trainer_base.py:173-175)
  */
 #ifndef LCI_H_
 #define LCI_H_
@@ -68,8 +72,9 @@ extern "C" {
  * 31: lci_layernorm_bwd dres2; 32: one-chunk selective scan without end-state workspaces (xend / xinit / sdt null),
  * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes);
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
- * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile. */
-#define LCI_ABI_VERSION 37
+ * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile;
+ * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef. */
+#define LCI_ABI_VERSION 38
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -493,6 +498,39 @@ int lci_adam_max_tensors(void);
 int lci_adam_step(float* const* p, const float* const* g, float* const* m, float* const* v, const float* const* step,
                   const long long* n, int nt, double lr, double beta1, double beta2, double weight_decay, double eps,
                   int adamw, int maximize, void* stream);
+/* lci_adam_step with three optional device-side inputs (null = absent; all null is lci_adam_step exactly). They let a
+ * captured step follow an LR schedule (trainer_base.py:181-182, :211-219; optim_base.py:101-115) and the grad-norm
+ * clip (:173-175) without any host value baked into the graph.
+ *   lr_dev : one f32 in device memory; the learning rate is (double)*lr_dev, read by the kernel (torch's tensor-lr
+ *            convention for capturable optimizers), for the step size and for AdamW's decoupled decay.
+ *   sched  : 8 HOST doubles {total_steps, end_step1, initial_lr, max_lr, min_lr, base_momentum, max_momentum, 0},
+ *            copied into the kernel arguments: lr and beta1 are torch's two-phase cosine OneCycleLR.get_lr (with
+ *            cycle_momentum) at step_num = *step[i] - 1, evaluated in f64 on the device once per workgroup. With
+ *            anneal(a, b, q) = b + (a - b) / 2.0 * (cos(pi q) + 1) and q = (step_num - start) / (end - start):
+ *              step_num <= end_step1 : start 0, end end_step1; lr = anneal(initial_lr, max_lr, q),
+ *                                      beta1 = anneal(max_momentum, base_momentum, q);
+ *              otherwise             : start end_step1, end total_steps - 1; lr = anneal(max_lr, min_lr, q),
+ *                                      beta1 = anneal(base_momentum, max_momentum, q).
+ *            torch's operation order, no FP contraction: only cos can differ from the host's value. The first bias
+ *            correction uses the scheduled beta1, as torch's does. sched together with lr_dev is an error (1).
+ *   gcoef  : one f32 in device memory; every gradient is multiplied by it in f32 before anything else (the rounding
+ *            of clip_grad_norm_'s in-place multiply). The gradients themselves are not written.
+ * lci_onecycle_eval: inspection entry. step (n f32, device) holds step counts in the optimizer's convention (already
+ * incremented); out (n, 2) f64 (device) = {lr, beta1} the update kernel uses at each, by the same device function.
+ * lci_grad_sumsq / lci_grad_clip_coef: clip_grad_norm_'s global 2-norm without atomics. lci_grad_sumsq writes one
+ * f64 sum of squares per 4096 elements of each of nt <= lci_adam_max_tensors() f32 tensors to part[0 ..
+ * lci_grad_sumsq_parts(n, nt)); longer lists take several calls on consecutive ranges of part. lci_grad_clip_coef
+ * sums nparts partials in a fixed order in f64: out[0] = norm (f32), out[1] = min(1, max_norm / (norm + 1e-6)) in f32.
+ * A NaN gradient gives a NaN norm and coefficient, an inf one coefficient 0 (error_if_nonfinite=False); both
+ * propagate into the update. No host sync. */
+int lci_adam_step_ex(float* const* p, const float* const* g, float* const* m, float* const* v,
+                     const float* const* step, const long long* n, int nt, double lr, double beta1, double beta2,
+                     double weight_decay, double eps, int adamw, int maximize, const float* lr_dev,
+                     const double* sched, const float* gcoef, void* stream);
+int lci_onecycle_eval(const float* step, int n, const double* sched, double* out, void* stream);
+long long lci_grad_sumsq_parts(const long long* n, int nt);
+int lci_grad_sumsq(const float* const* g, const long long* n, int nt, double* part, void* stream);
+int lci_grad_clip_coef(const double* part, long long nparts, double max_norm, float* out, void* stream);
 
 /* ------------------------------------------------------------------ CombinationEnhance loss (csrc/loss.hip)
  * The enhancement recipes' loss (--loss_func=CombinationEnhance: mse + charbonnier + gaussian3D, weights 1, no

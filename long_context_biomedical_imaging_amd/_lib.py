@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "liblci.so")
 LIB_PATH = os.environ.get("LCI_LIB_PATH", DEFAULT_LIB)   # override: kernel-variant A/B runs (no staleness check)
-ABI_VERSION = 37  # include/lci.h LCI_ABI_VERSION
+ABI_VERSION = 38  # include/lci.h LCI_ABI_VERSION
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -91,6 +91,10 @@ SIGNATURES = {
     "lci_hyena_filter_prep": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
     "lci_hyena_filter_fwd": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
     "lci_adam_step": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _I, _P],
+    "lci_adam_step_ex": [_P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _I, _I, _P, _P, _P, _P],
+    "lci_onecycle_eval": [_P, _I, _P, _P, _P],
+    "lci_grad_sumsq": [_P, _P, _I, _P, _P],
+    "lci_grad_clip_coef": [_P, _L, _D, _P, _P],
     "lci_hyena_filter_bwd": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "lci_enhance_loss": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lci_enhance_metrics": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -169,6 +173,8 @@ def load(path: str = LIB_PATH):
     lib.lci_dwconv_silu_bwd_part_rows.argtypes = [_I, _I]
     lib.lci_adam_max_tensors.restype = ctypes.c_int
     lib.lci_adam_max_tensors.argtypes = []
+    lib.lci_grad_sumsq_parts.restype = ctypes.c_longlong
+    lib.lci_grad_sumsq_parts.argtypes = [_P, _I]
     lib.lci_direct_conv_max_len.restype = ctypes.c_int
     lib.lci_direct_conv_max_len.argtypes = []
     lib.lci_direct_conv_dk_splits.restype = ctypes.c_int

@@ -3,7 +3,8 @@
 Mirrors /root/reference/setup/config_utils.py (Nestedspace :9-21, check_args :89-141) and
 setup/parsers/model_parser.py (--ViT.*, --Swin.* :29-47), plus the general flags the model and the
 training step read (--encoder_name, --decoder_name, --task_type, --height/--width/--time,
---no_in_channel/--no_out_channel, --batch_size, --use_amp, --ddp, --optim.*).
+--no_in_channel/--no_out_channel, --batch_size, --use_amp, --ddp, --optim.*, --scheduler_type, --scheduler.*,
+--num_epochs).
 """
 from __future__ import annotations
 
@@ -69,6 +70,19 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--optim.weight_decay", type=float, default=0.0)
     p.add_argument("--optim.beta1", type=float, default=0.90)
     p.add_argument("--optim.beta2", type=float, default=0.95)
+    # general_parser.py (--num_epochs, --scheduler_type) and setup/parsers/sched_parser.py:28-39 with its defaults;
+    # the reference adds only the chosen scheduler's flags, here all seven always parse. Deviation: the default is
+    # no scheduler (the reference's is ReduceLROnPlateau), so a run that names none trains as before.
+    p.add_argument("--num_epochs", type=int, default=50)
+    p.add_argument("--scheduler_type", type=lambda v: None if v in (None, "None", "none") else v, default=None,
+                   choices=["ReduceLROnPlateau", "StepLR", "OneCycleLR", None])
+    p.add_argument("--scheduler.patience", type=int, default=0)
+    p.add_argument("--scheduler.cooldown", type=int, default=0)
+    p.add_argument("--scheduler.min_lr", type=float, default=1e-8)
+    p.add_argument("--scheduler.factor", type=float, default=0.9)
+    p.add_argument("--scheduler.step_size", type=int, default=5)
+    p.add_argument("--scheduler.gamma", type=float, default=0.8)
+    p.add_argument("--scheduler.pct_start", type=float, default=0.3)
     # general_parser.py:109-110 (trainer_base.py:168-176)
     p.add_argument("--clip_grad_norm", type=float, default=0.0)
     p.add_argument("--iters_to_accumulate", type=int, default=1)

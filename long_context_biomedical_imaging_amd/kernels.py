@@ -2292,11 +2292,33 @@ def pointwise_small(x2: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor |
 
 
 # ------------------------------------------------------------------------------------------- optimizer step
+def _f32_scalar(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+        raise _lib.LciError(f"{what}: one f32 CUDA element expected")
+    return t.data_ptr()
+
+
+def _sched_array(sched):
+    """(total_steps, end_step1, initial_lr, max_lr, min_lr, base_momentum, max_momentum) -> the 8 host doubles of
+    lci_adam_step_ex / lci_onecycle_eval."""
+    vals = [float(v) for v in sched]
+    if len(vals) != 7:
+        raise _lib.LciError("one-cycle schedule: (total_steps, end_step1, initial_lr, max_lr, min_lr, base_momentum, "
+                            "max_momentum) expected")
+    return (ctypes.c_double * 8)(*vals, 0.0)
+
+
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1: float, beta2: float,
-              weight_decay: float, eps: float, decoupled: bool, maximize: bool) -> None:
+              weight_decay: float, eps: float, decoupled: bool, maximize: bool, *, lr_tensor=None, sched=None,
+              grad_coef=None) -> None:
     """One Adam / AdamW update of f32 CUDA tensors in place by csrc/optim.hip (lci_adam_step, up to
     lci_adam_max_tensors() tensors per launch); `steps` are the per-tensor device step counts, already incremented
-    (trainer_base.py:171-177 -> torch.optim.Adam / AdamW with optim_base.py:87-89's hyper-parameters)."""
+    (trainer_base.py:171-177 -> torch.optim.Adam / AdamW with optim_base.py:87-89's hyper-parameters).
+
+    lr_tensor: the learning rate as one f32 CUDA element read by the kernel (instead of `lr`); sched: the one-cycle
+    constants (total_steps, end_step1, initial_lr, max_lr, min_lr, base_momentum, max_momentum): learning rate and
+    beta1 from torch's OneCycleLR at each tensor's device step count (instead of `lr`, `beta1`); grad_coef: one f32
+    CUDA element every gradient is multiplied by first (kernels.grad_clip_coef). See lci_adam_step_ex."""
     if not params:
         return
     lib = _lib.load()
@@ -2304,15 +2326,68 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1: flo
     for t in (*params, *grads, *exp_avgs, *exp_avg_sqs):
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
             raise _lib.LciError("adam_step: f32 contiguous CUDA tensors only")
+    ex = lr_tensor is not None or sched is not None or grad_coef is not None
+    if ex:
+        if isinstance(lr, torch.Tensor):
+            lr = 0.0   # unused: the kernel reads lr_tensor / the schedule
+        tail = (None if lr_tensor is None else _f32_scalar(lr_tensor, "adam_step lr_tensor"),
+                None if sched is None else _sched_array(sched),
+                None if grad_coef is None else _f32_scalar(grad_coef, "adam_step grad_coef"))
     st = _lib.stream_of(params[0])
     for i0 in range(0, len(params), per):
         sl = slice(i0, i0 + per)
         n = len(params[sl])
         arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
         sizes = (ctypes.c_longlong * n)(*[t.numel() for t in params[sl]])
-        _lib.call("lci_adam_step", arr(params[sl]), arr(grads[sl]), arr(exp_avgs[sl]), arr(exp_avg_sqs[sl]),
-                  arr(steps[sl]), sizes, n, float(lr), float(beta1), float(beta2), float(weight_decay), float(eps),
-                  int(decoupled), int(maximize), st)
+        args = (arr(params[sl]), arr(grads[sl]), arr(exp_avgs[sl]), arr(exp_avg_sqs[sl]),
+                arr(steps[sl]), sizes, n, float(lr), float(beta1), float(beta2), float(weight_decay), float(eps),
+                int(decoupled), int(maximize))
+        if ex:
+            _lib.call("lci_adam_step_ex", *args, *tail, st)
+        else:
+            _lib.call("lci_adam_step", *args, st)
+
+
+def onecycle_eval(steps: torch.Tensor, sched) -> torch.Tensor:
+    """(n, 2) f64 {lr, beta1} that the update kernel's one-cycle schedule gives at each of the n f32 CUDA step counts
+    in `steps` (the optimizer's convention: a count already incremented for its update, so the schedule is evaluated
+    at steps - 1); sched as for adam_step. The same device function, for inspection and tests; no host sync."""
+    if not (steps.is_cuda and steps.dtype == torch.float32 and steps.is_contiguous()):
+        raise _lib.LciError("onecycle_eval: f32 contiguous CUDA step counts only")
+    out = torch.empty(steps.numel(), 2, device=steps.device, dtype=torch.float64)
+    _lib.call("lci_onecycle_eval", steps.data_ptr(), steps.numel(), _sched_array(sched), out.data_ptr(),
+              _lib.stream_of(steps))
+    return out
+
+
+def grad_clip_coef(grads, max_norm: float):
+    """nn.utils.clip_grad_norm_'s total 2-norm of the f32 CUDA tensors `grads` and its clip coefficient
+    min(1, max_norm / (norm + 1e-6)) (trainer_base.py:173-175) as two f32 device scalars (norm, coef), by
+    lci_grad_sumsq + lci_grad_clip_coef: no atomics, no host sync; the gradients are not modified (pass coef to
+    adam_step's grad_coef)."""
+    grads = list(grads)
+    if not grads:
+        raise _lib.LciError("grad_clip_coef: no gradients")
+    for t in grads:
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.LciError("grad_clip_coef: f32 contiguous CUDA tensors only")
+    lib = _lib.load()
+    per = lib.lci_adam_max_tensors()
+    dev = grads[0].device
+    st = _lib.stream_of(grads[0])
+    calls, total = [], 0
+    for i0 in range(0, len(grads), per):
+        gs = grads[i0:i0 + per]
+        n = len(gs)
+        sizes = (ctypes.c_longlong * n)(*[t.numel() for t in gs])
+        calls.append(((ctypes.c_void_p * n)(*[t.data_ptr() for t in gs]), sizes, n, total))
+        total += lib.lci_grad_sumsq_parts(sizes, n)
+    part = torch.empty(max(1, total), device=dev, dtype=torch.float64)
+    out = torch.empty(2, device=dev, dtype=torch.float32)
+    for ptrs, sizes, n, off in calls:
+        _lib.call("lci_grad_sumsq", ptrs, sizes, n, part.data_ptr() + 8 * off, st)
+    _lib.call("lci_grad_clip_coef", part.data_ptr(), total, float(max_norm), out.data_ptr(), st)
+    return out[0], out[1]
 
 
 # ------------------------------------------------------------------------------------------- enhancement loss

@@ -3,7 +3,8 @@
 One process per GPU (torchrun), torch.distributed over RCCL (backend "nccl" on ROCm). The model is wrapped
 in DDP exactly as the reference does (trainer_base.py:98); its bucketed fp32 gradient all-reduce runs on
 RCCL over xGMI, overlapped with backward. Per step (trainer_base.py:157-182): forward under autocast,
-loss, backward, optimizer step, zero_grad.
+loss, backward, optimizer step, zero_grad, and the LR scheduler's step (OneCycleLR per update :181-182, StepLR /
+ReduceLROnPlateau per epoch :211-219 -> TrainStep.end_epoch).
 
 Documented deviations from the reference step:
   * autocast dtype is bf16 on gfx950 (the reference's utils/status.py:50-58 `support_bfloat16` checks for
@@ -18,7 +19,10 @@ Documented deviations from the reference step:
 """
 from __future__ import annotations
 
+import argparse
+import math
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -68,7 +72,13 @@ class _LciAdamStep:
     state_dict are torch's own and checkpoints move between the two; only the arithmetic kernel differs (the same
     formulas: csrc/optim.hip). torch's fused kernel gave each 64-K-element chunk one workgroup (~1000 over a
     SwinUNETR step at ~1 TB/s); this one streams at the HBM rate. Groups with options the reference never sets
-    (amsgrad, complex or non-f32 parameters, a tensor lr, differentiable) take torch's fused update.
+    (amsgrad, complex or non-f32 parameters, differentiable) take torch's fused update.
+
+    LR schedules reach the kernel through device memory, so a captured step follows them: a tensor `group["lr"]` of
+    one CUDA f32 element (torch's convention for capturable optimizers; StepLR / ReduceLROnPlateau fill_ it) is read
+    by the kernel, and a registered LciOneCycleLR is evaluated there from each tensor's step count (learning rate and
+    beta1; param_groups' "lr" / "betas" are then only the host mirror its step() keeps). `_lci_grad_coef`, set by
+    TrainStep around a clipped update, multiplies every gradient in the kernel.
 
     torch's fused Adam declares `_step_supports_amp_scaling`, so a GradScaler (the reference's loop,
     trainer_base.py:116,171-182) does not unscale / inf-check for it but hands the optimizer `grad_scale` and
@@ -76,6 +86,17 @@ class _LciAdamStep:
     the update skipped on a device-side inf / NaN), exactly what the class it derives from does."""
 
     _decoupled = False
+    _lci_sched = None       # weakref to the LciOneCycleLR whose schedule the kernel evaluates (set by its constructor)
+    _lci_grad_coef = None   # one f32 CUDA element every gradient is multiplied by in the next step (TrainStep's clip)
+
+    def onecycle_constants(self, group):
+        """The one-cycle constants of `group` for kernels.adam_step(sched=...), read from the registered scheduler and
+        the keys it keeps in the group (so a loaded state_dict of either is followed); None without a scheduler."""
+        sched = self._lci_sched() if self._lci_sched is not None else None
+        if sched is None:
+            return None
+        return (sched.total_steps, sched._schedule_phases[0]["end_step"], group["initial_lr"], group["max_lr"],
+                group["min_lr"], group["base_momentum"], group["max_momentum"])
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -85,16 +106,27 @@ class _LciAdamStep:
                 loss = closure()
         grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         scaled = grad_scale is not None or found_inf is not None
+        coef = self._lci_grad_coef
         for group in self.param_groups:
             params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps = [], [], [], [], [], []
             has_complex = self._init_group(group, params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps)
             if not params:
                 continue
             beta1, beta2 = group["betas"]
-            if (scaled or has_complex or group["amsgrad"] or group.get("differentiable")
-                    or isinstance(group["lr"], torch.Tensor)
+            lr, sched = group["lr"], self.onecycle_constants(group)
+            # a device learning rate (torch's convention for capturable optimizers: StepLR / ReduceLROnPlateau fill_
+            # it) is read by the kernel; the one-cycle schedule, evaluated there, takes precedence over either form
+            lr_tensor = lr if isinstance(lr, torch.Tensor) and sched is None else None
+            bad_lr = lr_tensor is not None and not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1)
+            if (scaled or has_complex or group["amsgrad"] or group.get("differentiable") or bad_lr
                     or any(p.dtype != torch.float32 or not p.is_cuda for p in params)
                     or any(g.is_sparse or not g.is_contiguous() for g in grads)):
+                if sched is not None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+                    # torch's kernel would take the host mirror's lr / betas: constants of the graph from then on
+                    raise ValueError("LciAdam: a group that takes torch's fused update (amsgrad, non-f32 parameters, "
+                                     "a GradScaler, ...) cannot follow OneCycleLR inside a captured step")
+                if coef is not None:
+                    torch._foreach_mul_(grads, coef)
                 _fused_adam(params, grads, exp_avgs, exp_avg_sqs, max_sqs, steps, grad_scale, found_inf,
                                              amsgrad=group["amsgrad"], has_complex=has_complex, beta1=beta1,
                                              beta2=beta2, lr=group["lr"], weight_decay=group["weight_decay"],
@@ -103,8 +135,9 @@ class _LciAdamStep:
                 continue
             torch._foreach_add_(steps, 1)
             from . import kernels
-            kernels.adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, group["lr"], beta1, beta2,
-                              group["weight_decay"], group["eps"], self._decoupled, group["maximize"])
+            kernels.adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2,
+                              group["weight_decay"], group["eps"], self._decoupled, group["maximize"],
+                              lr_tensor=lr_tensor, sched=sched, grad_coef=coef)
         return loss
 
 
@@ -120,14 +153,47 @@ class LciAdamW(_LciAdamStep, torch.optim.AdamW):
         torch.optim.AdamW.__init__(self, params, fused=True, **kw)
 
 
+class LciOneCycleLR(torch.optim.lr_scheduler.OneCycleLR):
+    """torch's OneCycleLR (the recipes' --scheduler_type, optim_base.py:113-115) whose schedule an LciAdam / LciAdamW
+    evaluates inside its update kernel, from each tensor's device step count (csrc/optim.hip: learning rate and, as
+    cycle_momentum is on by default, beta1). The optimizer's step therefore follows the schedule inside a captured
+    graph too, where the host values `step()` writes would be baked in at capture.
+
+    Everything on the host is torch's: the constructor's arguments and errors, `step()` (which keeps the host mirror:
+    param_groups' "lr" and "betas" for logging, last_epoch, and the ValueError past total_steps) and the state_dict,
+    which holds no extra key, so a checkpoint's sched_state loads into either class. The constructor only registers
+    itself with the optimizer, which reads total_steps and the first phase's end from it and the remaining constants
+    from the keys torch keeps in each param group. With any other optimizer (SGD, NAdam, torch's Adam, CPU), or with
+    an option the kernel does not evaluate (three_phase, linear annealing, cycle_momentum=False), nothing is
+    registered and the class is torch's."""
+
+    def __init__(self, optimizer, *args, **kwargs):
+        super().__init__(optimizer, *args, **kwargs)
+        if (isinstance(optimizer, _LciAdamStep) and len(self._schedule_phases) == 2
+                and self._anneal_func_type == "cos" and self.cycle_momentum):
+            optimizer._lci_sched = weakref.ref(self)
+
+
+def _no_scheduler(config):
+    return getattr(config, "scheduler_type", None) in (None, "None", "none")
+
+
 def build_optimizer(params, config):
     """The reference's optimizers (optim_base.py:87-93; same hyper-parameters). On the GPU Adam / AdamW update on
     csrc/optim.hip (LciAdam / LciAdamW, torch-compatible state); LCI_HIP_ADAM=0 uses torch's fused kernel,
-    LCI_FUSED_ADAM=0 torch's multi-tensor one (~150 launches per SwinUNETR step, 6.4 ms per C3 step)."""
+    LCI_FUSED_ADAM=0 torch's multi-tensor one (~150 launches per SwinUNETR step, 6.4 ms per C3 step).
+
+    With --scheduler_type StepLR / ReduceLROnPlateau an LciAdam / LciAdamW gets its learning rate as one f32 device
+    element: torch's scheduler classes then update it in place and a captured step sees the change."""
     o = config.optim
     params = list(params)
     fused = all(p.is_cuda for p in params) and os.environ.get("LCI_FUSED_ADAM", "1") != "0"
     hip = fused and os.environ.get("LCI_HIP_ADAM", "1") != "0"
+    # only LciAdam / LciAdamW: SGD / NAdam keep torch's host float, which torch's schedulers then update as ever
+    if (hip and params and config.optim_type in ("adam", "adamw")
+            and getattr(config, "scheduler_type", None) in ("StepLR", "ReduceLROnPlateau")):
+        o = argparse.Namespace(**vars(o))
+        o.lr = torch.tensor(float(o.lr), device=params[0].device, dtype=torch.float32)
     if config.optim_type == "adam":
         if hip:
             return LciAdam(params, lr=o.lr, betas=(o.beta1, o.beta2), weight_decay=o.weight_decay)
@@ -145,6 +211,32 @@ def build_optimizer(params, config):
     raise NotImplementedError(f"Optimizer not implemented: {config.optim_type}")
 
 
+def compute_total_updates(config, num_samples: int, world: int = 1) -> int:
+    """optim_utils.py:10-21: the optimizer updates of a whole run, OneCycleLR's total_steps."""
+    per_update = config.batch_size * max(1, int(getattr(config, "iters_to_accumulate", 1) or 1)) * world
+    return int(math.ceil(num_samples / per_update) * config.num_epochs)
+
+
+def build_scheduler(optim, config, total_updates=None):
+    """The reference's schedulers with its constructor arguments (optim_base.py:101-120); None for
+    --scheduler_type None. OneCycleLR (every recipe's choice) needs `total_updates` (compute_total_updates) and is an
+    LciOneCycleLR: evaluated in the update kernel for LciAdam / LciAdamW, plain torch for any other optimizer."""
+    if _no_scheduler(config):
+        return None
+    s, kind = config.scheduler, config.scheduler_type
+    if kind == "ReduceLROnPlateau":
+        return torch.optim.lr_scheduler.ReduceLROnPlateau(optim, mode="min", factor=s.factor, patience=s.patience,
+                                                          cooldown=s.cooldown, min_lr=s.min_lr)
+    if kind == "StepLR":
+        return torch.optim.lr_scheduler.StepLR(optim, step_size=s.step_size, gamma=s.gamma, last_epoch=-1)
+    if kind == "OneCycleLR":
+        if total_updates is None:
+            raise ValueError("OneCycleLR needs total_updates (trainer.compute_total_updates)")
+        return LciOneCycleLR(optim, max_lr=config.optim.lr, total_steps=int(total_updates), pct_start=s.pct_start,
+                             anneal_strategy="cos")
+    raise NotImplementedError(f"Scheduler not implemented: {kind}")
+
+
 def loss_fn(config):
     if config.loss_func == "CrossEntropy":
         return nn.CrossEntropyLoss()
@@ -157,7 +249,9 @@ def loss_fn(config):
 class TrainStep:
     """model (already on device) -> DDP -> step(inputs, targets) returns the loss tensor (no host sync)."""
 
-    def __init__(self, model, config, device, ddp: bool):
+    def __init__(self, model, config, device, ddp: bool, total_updates: int | None = None):
+        """total_updates: the optimizer updates of the whole run (compute_total_updates), needed by --scheduler_type
+        OneCycleLR only (ValueError without it)."""
         self.device = device
         self.model = model
         if ddp:
@@ -169,9 +263,18 @@ class TrainStep:
                                                              broadcast_buffers=False, gradient_as_bucket_view=True,
                                                              **kw)
         self.optim = build_optimizer(self.model.parameters(), config)
+        # optim_base.py:101-120; stepped per update (OneCycleLR, step()) or per epoch (end_epoch())
+        self.sched_type = None if _no_scheduler(config) else config.scheduler_type
+        self.sched = build_scheduler(self.optim, config, total_updates)
+        self.hold_sched = False   # GraphedStep: the captured step must not advance the host mirror
         self.loss_func = loss_fn(config)
         self.use_amp = bool(config.use_amp)
         self.clip = float(getattr(config, "clip_grad_norm", 0.0) or 0.0)
+        # the clip on a CUDA LciAdam(W): norm and coefficient by kernels.grad_clip_coef, the multiply inside the
+        # update kernel (p.grad itself stays unscaled; it is zeroed right after the step)
+        self.fused_clip = (self.clip > 0 and isinstance(self.optim, _LciAdamStep)
+                           and all(p.is_cuda and p.dtype == torch.float32 for p in self.model.parameters()))
+        self.grad_norm = None     # the last clipped update's total gradient norm (device tensor)
         self.accum = max(1, int(getattr(config, "iters_to_accumulate", 1) or 1))
         self.micro = 0   # micro-batches since the last optimizer step (trainer_base.py:172 `idx`)
         self.dup_batch1 = any(isinstance(m, nn.modules.batchnorm._BatchNorm) for m in model.modules())
@@ -199,12 +302,42 @@ class TrainStep:
         if update is None:
             update = self.micro % self.accum == 0
         if update:
-            if self.clip > 0:
-                nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
-            self.optim.step()
-            self.optim.zero_grad(set_to_none=True)
-            self.micro = 0
+            self._update()
         return loss.detach()
+
+    def _update(self):
+        """trainer_base.py:173-182: clip, optimizer step, zero_grad, and OneCycleLR's per-update step."""
+        grads = None
+        if self.fused_clip:
+            grads = [p.grad for p in self.model.parameters() if p.grad is not None]
+            if not grads or any(g.is_sparse or g.dtype != torch.float32 or not g.is_contiguous() for g in grads):
+                grads = None
+        if grads is not None:
+            from . import kernels
+            self.grad_norm, self.optim._lci_grad_coef = kernels.grad_clip_coef(grads, self.clip)
+            try:
+                self.optim.step()
+            finally:
+                self.optim._lci_grad_coef = None
+        else:
+            if self.clip > 0:
+                self.grad_norm = nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
+            self.optim.step()
+        self.optim.zero_grad(set_to_none=True)
+        self.micro = 0
+        if self.sched_type == "OneCycleLR" and not self.hold_sched:
+            self.sched.step()
+
+    def end_epoch(self, loss=None):
+        """trainer_base.py:211-219: the per-epoch schedulers. StepLR steps; ReduceLROnPlateau steps on `loss` (the
+        epoch's validation loss, or the last step's as the reference falls back to). OneCycleLR and no scheduler:
+        nothing to do."""
+        if self.sched_type == "StepLR":
+            self.sched.step()
+        elif self.sched_type == "ReduceLROnPlateau":
+            if loss is None:
+                raise ValueError("end_epoch: ReduceLROnPlateau steps on a loss")
+            self.sched.step(float(loss))
 
 
 class GraphedStep:
@@ -217,10 +350,19 @@ class GraphedStep:
     per Swin-tiny step) is paid once at capture. Single process only (no DDP: its all-reduce hooks are not part
     of the capture here); the optimizer runs with capturable=True (fused Adam / AdamW keep their step on device).
 
-    Constructing it TRAINS: the `warmup` side-stream steps and the captured step are real optimizer steps on the
-    static batch (warmup + 1 updates before the first replay). If the capture fails, the optimizer's `capturable`
+    Constructing it TRAINS: the `warmup` side-stream steps are real optimizer steps on the static batch (`warmup`
+    updates before the first replay; the capture itself records the step and runs nothing). If the capture fails, the optimizer's `capturable`
     flags are restored before the error propagates (the weights keep the warm-up updates). Gradient accumulation
     (iters_to_accumulate > 1) is refused: the graph replays one fixed step, always with the optimizer update.
+
+    With an LR scheduler the optimizer must be LciAdam / LciAdamW (ValueError otherwise): its kernel evaluates
+    OneCycleLR from the device step count and reads StepLR's / ReduceLROnPlateau's learning rate from a device tensor
+    (step those with `trainer.end_epoch()` between replays). OneCycleLR's host mirror advances once per warm-up step
+    and once per replay, not for the capture, so after any sequence of warm-up, capture and replays
+    `sched.last_epoch == int(optim.state[p]["step"])`; a replay past total_steps raises torch's ValueError before
+    anything is launched. Per replay the host does the mirror's float arithmetic and nothing else. A param group
+    that would take torch's fused update instead of the HIP kernel (amsgrad, non-f32 parameters, a GradScaler) under
+    OneCycleLR makes the capture raise ValueError: its host lr / betas would become constants of the graph.
     """
 
     def __init__(self, trainer: "TrainStep", inputs, targets, warmup: int = 2):
@@ -228,6 +370,15 @@ class GraphedStep:
             raise ValueError("GraphedStep: single-process TrainStep only")
         if trainer.accum != 1:
             raise ValueError("GraphedStep: iters_to_accumulate > 1 is not supported (the graph always updates)")
+        # a schedule must reach the captured update through device memory: LciAdam / LciAdamW evaluate OneCycleLR in
+        # the kernel and read StepLR's / ReduceLROnPlateau's learning rate from a device tensor; a host float of any
+        # other optimizer would be baked into the graph at capture
+        if trainer.sched is not None and not (
+                isinstance(trainer.optim, _LciAdamStep)
+                and all(trainer.optim.onecycle_constants(g) is not None if trainer.sched_type == "OneCycleLR"
+                        else isinstance(g["lr"], torch.Tensor) for g in trainer.optim.param_groups)):
+            raise ValueError("GraphedStep: an LR scheduler needs the LciAdam / LciAdamW optimizer (the captured "
+                             "update reads the schedule on the device)")
         # TrainStep.step's duplication of a batch of 1, once on the static buffers; replays duplicate exactly when
         # the capture did (a BatchNorm model captured at batch 1), never a genuine batch of 2
         self.dup = inputs.shape[0] == 1 and trainer.dup_batch1
@@ -247,6 +398,9 @@ class GraphedStep:
             torch.cuda.current_stream(inputs.device).wait_stream(side)
             torch.cuda.synchronize(inputs.device)
             self.graph = torch.cuda.CUDAGraph()
+            # the capture runs nothing, so it must not advance the scheduler's host mirror either: the mirror moves
+            # once per warm-up step and once per replay, and last_epoch stays equal to the device step count
+            trainer.hold_sched = True
             # relaxed: the kernels' one-time launch attributes (hipFuncSetAttribute) are legal during the capture
             with torch.cuda.graph(self.graph, capture_error_mode="relaxed"):
                 self.loss = trainer.step(inputs, targets, update=True)
@@ -254,6 +408,8 @@ class GraphedStep:
             for g, c in saved:
                 g["capturable"] = c
             raise
+        finally:
+            trainer.hold_sched = False
 
     @staticmethod
     def _dup(t):
@@ -268,6 +424,16 @@ class GraphedStep:
             if self.dup and targets.shape[0] == 1:
                 targets = self._dup(targets)
             self.targets.copy_(targets)
+        sched = self.trainer.sched
+        if self.trainer.sched_type == "OneCycleLR":
+            # the host mirror of the update about to be replayed (float arithmetic only); past total_steps torch's
+            # ValueError stops the replay before anything is launched, with the mirror left where the device is
+            try:
+                sched.step()
+            except ValueError:
+                sched.last_epoch -= 1
+                sched._step_count -= 1
+                raise
         self.graph.replay()
         return self.loss
 
@@ -320,4 +486,5 @@ def synthetic_batch(config, batch, device, seed):
     return x.to(device), y.to(device)
 
 
-__all__ = ["init_distributed", "TrainStep", "EvalStep", "synthetic_batch", "LciAdam", "LciAdamW", "F"]
+__all__ = ["init_distributed", "TrainStep", "EvalStep", "synthetic_batch", "LciAdam", "LciAdamW", "LciOneCycleLR",
+           "build_scheduler", "compute_total_updates", "F"]
