@@ -74,7 +74,7 @@ extern "C" {
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
  * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile;
  * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef. */
-#define LCI_ABI_VERSION 38
+#define LCI_ABI_VERSION 39
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -583,6 +583,41 @@ int lci_enhance_metrics(const void* outputs, int out_dtype, const void* targets,
 long long lci_seg_f1_ws_bytes(int B, int C, long long S);
 int lci_seg_f1(const void* logits, int dtype, const long long* labels, long long* counts, float* result, void* ws,
                int B, int C, long long S, void* stream);
+
+/* ------------------------------------------------------------------ classification metrics (csrc/class_metrics.hip)
+ * acc_1, AUROC and F1 of the reference's metric manager for task_type=class (metrics_base.py:59-78, 268-285, 304-376),
+ * per step or exactly over every sample of an evaluation epoch (--exact_metrics). A restatement of what torchmetrics
+ * 1.4.1 computes there; it was not compared with torchmetrics itself. No host sync, integer atomics only: bitwise
+ * reproducible.
+ *   Scores p = softmax(logits (B, C), dim 1), 2 <= C <= 64, logits f32 or bf16 (dtype codes above), evaluated in f64
+ *   and rounded once to f32; labels (B,) int64. K score columns are kept per row: K = 1 for C == 2 (the 'binary' task:
+ *   p[:, 1], positive class 1), K = C otherwise (column c against the rest). A label outside [0, C) is never a
+ *   positive and never a correct prediction.
+ *   Per column c with P positives, Q = n - P negatives, on the stored f32 scores s, compared bit for bit:
+ *     U2 = sum over positives i and negatives j of 2 [s_i > s_j] + [s_i == s_j];
+ *     auroc_c = U2 / (2 P Q), 0 when P Q == 0: the area under the exact ROC curve (distinct thresholds, trapezoids).
+ *   C == 2: pred = [s > 0.5] (strict: equal logits predict 0); acc_1 = the fraction with pred == label;
+ *     f1 = 2 tp / (2 tp + fp + fn) of class 1, 0 for a zero denominator; auroc = auroc_0.
+ *   C > 2: pred = the first index of the maximum of the stored row; acc_1 likewise; f1 = the mean of the per-class
+ *     2 tp / (2 tp + fp + fn) over the classes with tp + fp + fn > 0 (lci_seg_f1's rule); auroc = the mean of auroc_c
+ *     over all C columns (a column with P Q == 0 contributes 0).
+ * lci_class_append: softmax rows of `logits` to probs[count + b] ((capacity, K) f32) and labels to
+ *   label_buf[count + b], then *count += B (count: one int64 in device memory, read by every thread before a follow-up
+ *   kernel changes it, so a captured append replays). Rows at or past `capacity` are dropped but still counted:
+ *   *count > capacity afterwards tells the overflow. A row's bits do not depend on where it lands.
+ * lci_class_score: n stored rows (1 <= n < 2^31) -> counts int64 [6 K + 1]: (K, 6) = tp, fp, fn, P, Q, U2 per column,
+ *   then the number of correct predictions; result[3] f64 = {acc_1, auroc, f1}.
+ * lci_class_metrics: softmax + score of one batch without a buffer, bit-identical to append + score of that batch.
+ *   ws: lci_class_metrics_ws_bytes(B, C) bytes (-1 for a bad shape), 16-byte aligned.
+ * lci_class_tile(axis): the pair count's tile extents: 0 = rows i per workgroup, 1 = rows j per LDS tile. */
+int lci_class_tile(int axis);
+long long lci_class_metrics_ws_bytes(int B, int C);
+int lci_class_append(const void* logits, int dtype, const long long* labels, float* probs, long long* label_buf,
+                     long long* count, long long capacity, int B, int C, void* stream);
+int lci_class_score(const float* probs, const long long* labels, long long* counts, double* result, long long n,
+                    int C, void* stream);
+int lci_class_metrics(const void* logits, int dtype, const long long* labels, long long* counts, double* result,
+                      void* ws, int B, int C, void* stream);
 
 #ifdef __cplusplus
 }

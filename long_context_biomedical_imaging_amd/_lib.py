@@ -14,7 +14,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(HERE, "liblci.so")
 LIB_PATH = os.environ.get("LCI_LIB_PATH", DEFAULT_LIB)   # override: kernel-variant A/B runs (no staleness check)
-ABI_VERSION = 38  # include/lci.h LCI_ABI_VERSION
+ABI_VERSION = 39  # include/lci.h LCI_ABI_VERSION
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -99,6 +99,9 @@ SIGNATURES = {
     "lci_enhance_loss": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "lci_enhance_metrics": [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "lci_seg_f1": [_P, _I, _P, _P, _P, _P, _I, _I, _L, _P],
+    "lci_class_append": [_P, _I, _P, _P, _P, _P, _L, _I, _I, _P],
+    "lci_class_score": [_P, _P, _P, _P, _L, _I, _P],
+    "lci_class_metrics": [_P, _I, _P, _P, _P, _P, _I, _I, _P],
 }
 
 _lib = None
@@ -187,6 +190,10 @@ def load(path: str = LIB_PATH):
     lib.lci_seg_f1_ws_bytes.argtypes = [_I, _I, _L]
     lib.lci_ssim_tile.restype = ctypes.c_int
     lib.lci_ssim_tile.argtypes = [_I]
+    lib.lci_class_tile.restype = ctypes.c_int
+    lib.lci_class_tile.argtypes = [_I]
+    lib.lci_class_metrics_ws_bytes.restype = ctypes.c_longlong
+    lib.lci_class_metrics_ws_bytes.argtypes = [_I, _I]
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argt

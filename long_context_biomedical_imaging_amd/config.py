@@ -3,7 +3,7 @@
 Mirrors /root/reference/setup/config_utils.py (Nestedspace :9-21, check_args :89-141) and
 setup/parsers/model_parser.py (--ViT.*, --Swin.* :29-47), plus the general flags the model and the
 training step read (--encoder_name, --decoder_name, --task_type, --height/--width/--time,
---no_in_channel/--no_out_channel, --batch_size, --use_amp, --ddp, --optim.*, --scheduler_type, --scheduler.*,
+--no_in_channel/--no_out_channel, --batch_size, --exact_metrics, --use_amp, --ddp, --optim.*, --scheduler_type, --scheduler.*,
 --num_epochs).
 """
 from __future__ import annotations
@@ -50,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--encoder_name", type=str, default="ViT", choices=["ViT", "Swin", "Identity"])
     p.add_argument("--decoder_name", type=str, default="ViTUNETR")
     p.add_argument("--task_type", type=str, default="seg", choices=["class", "seg", "enhance"])
+    # general_parser.py:103: classification metrics once over every prediction of an evaluation epoch (metrics.ClassMetrics)
+    p.add_argument("--exact_metrics", type=str_to_bool, default=False)
     p.add_argument("--loss_func", type=str, default="CrossEntropy", choices=["CrossEntropy", "MSE", "CombinationEnhance"])
     p.add_argument("--height", type=int, default=512)
     p.add_argument("--width", type=int, default=512)
@@ -114,6 +116,8 @@ def check_args(config):
     """The parts of config_utils.check_args (:89-141) that affect the model."""
     if "LOCAL_RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         config.ddp = True
+    if getattr(config, "exact_metrics", False) and getattr(config, "task_type", None) != "class":
+        raise NotImplementedError("Exact metrics not implemented for task types other than class")   # metrics_base.py:274
     for enc in ("ViT", "Swin"):
         ns = getattr(config, enc, None)
         if ns is None:

@@ -2514,3 +2514,97 @@ def seg_f1(logits: torch.Tensor, labels: torch.Tensor):
         "lci_seg_f1", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), counts.data_ptr(),
         res.data_ptr(), ws.data_ptr(), B, C, S, _lib.stream_of(logits)))
     return res[0], counts
+
+
+# ------------------------------------------------------------------------------------ classification metrics
+CLASS_TILE = (2048, 1024)   # csrc/class_metrics.hip's pair count (lci_class_tile): rows i per workgroup, rows j per LDS tile
+
+
+def _class_check(name, logits, labels):
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError(f"{name}: logits {tuple(logits.shape)} must be (B, C) and labels {tuple(labels.shape)} (B,)")
+    B, C = logits.shape
+    if not 2 <= C <= 64:
+        raise ValueError(f"{name}: C = {C} outside [2, 64]")
+    if logits.dtype not in _METRIC_DTYPES:
+        raise ValueError(f"{name}: logits dtype {logits.dtype} (f32 or bf16 only)")
+    if labels.dtype != torch.int64:
+        raise ValueError(f"{name}: labels dtype {labels.dtype} (int64 only)")
+    if B < 1:
+        raise ValueError(f"{name}: empty batch")
+    return B, C
+
+
+def _class_columns(C: int) -> int:
+    return 1 if C == 2 else C
+
+
+def _class_out(K, device):
+    counts = torch.empty(6 * K + 1, device=device, dtype=torch.int64)
+    return counts, torch.empty(3, device=device, dtype=torch.float64)
+
+
+def class_append(logits: torch.Tensor, labels: torch.Tensor, probs: torch.Tensor, label_buf: torch.Tensor,
+                 count: torch.Tensor) -> None:
+    """The --exact_metrics buffer of an evaluation epoch (metrics/metrics_base.py:304-376) on csrc/class_metrics.hip:
+    the f32 softmax rows of logits (B, C) f32 / bf16, 2 <= C <= 64, go to probs[count + b] and labels (B,) int64 to
+    label_buf[count + b], then count (one int64 CUDA element) grows by B, all on the device: no host sync, and a
+    captured call appends again on every replay. probs is (capacity, K) f32 with K = 1 for C == 2 (it holds p[:, 1])
+    and K = C otherwise, label_buf (capacity,) int64. Rows at or past capacity are dropped but counted, so
+    count > capacity afterwards shows the overflow."""
+    B, C = _class_check("class_append", logits, labels)
+    K = _class_columns(C)
+    if probs.dim() != 2 or probs.shape[1] != K or probs.dtype != torch.float32 or probs.shape[0] < 1:
+        raise ValueError(f"class_append: probs {tuple(probs.shape)} {probs.dtype} must be (capacity, {K}) f32")
+    if tuple(label_buf.shape) != (probs.shape[0],) or label_buf.dtype != torch.int64:
+        raise ValueError(f"class_append: label_buf {tuple(label_buf.shape)} {label_buf.dtype} must be "
+                         f"({probs.shape[0]},) int64")
+    if count.numel() != 1 or count.dtype != torch.int64:
+        raise ValueError("class_append: count must be one int64 element")
+    logits, labels = logits.detach().contiguous(), labels.contiguous()
+    _lib.require_gpu(logits, labels, probs, label_buf, count)
+    traffic = float(logits.numel() * logits.element_size() + B * (8 + 8 + 4 * K))
+    KernelTimer.run("class_append", traffic, logits, lambda: _lib.call(
+        "lci_class_append", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), probs.data_ptr(),
+        label_buf.data_ptr(), count.data_ptr(), probs.shape[0], B, C, _lib.stream_of(logits)))
+
+
+def class_score(probs: torch.Tensor, labels: torch.Tensor, n: int, C: int):
+    """acc_1, AUROC and F1 over the first n stored rows of probs (>= n, K) f32 and labels (>= n,) int64 (K = 1 for
+    C == 2, else C), as class_append leaves them. Returns (result, counts, correct) on the device, no host sync:
+    result (3,) f64 = acc_1, auroc, f1; counts (K, 6) int64 = tp, fp, fn, P, Q and U2 per score column, where U2 is
+    the exact integer sum over positive / negative pairs of 2 [s_i > s_j] + [s_i == s_j] and auroc_c = U2 / (2 P Q);
+    correct, the number of correct predictions (include/lci.h states every formula)."""
+    if not 2 <= C <= 64:
+        raise ValueError(f"class_score: C = {C} outside [2, 64]")
+    K = _class_columns(C)
+    if probs.dim() != 2 or probs.shape[1] != K or probs.dtype != torch.float32:
+        raise ValueError(f"class_score: probs {tuple(probs.shape)} {probs.dtype} must be (rows, {K}) f32")
+    if labels.dim() != 1 or labels.dtype != torch.int64:
+        raise ValueError(f"class_score: labels {tuple(labels.shape)} {labels.dtype} must be (rows,) int64")
+    n = int(n)
+    if not 1 <= n <= min(probs.shape[0], labels.shape[0]) or n >= 2 ** 31:
+        raise ValueError(f"class_score: n = {n} outside [1, min({probs.shape[0]}, {labels.shape[0]}, 2^31 - 1)]")
+    _lib.require_gpu(probs, labels)
+    counts, res = _class_out(K, probs.device)
+    KernelTimer.run("class_score", float(n) * n * K, probs, lambda: _lib.call(
+        "lci_class_score", probs.data_ptr(), labels.data_ptr(), counts.data_ptr(), res.data_ptr(), n, C,
+        _lib.stream_of(probs)))
+    return res, counts[:-1].view(K, 6), counts[-1]
+
+
+def class_metrics(logits: torch.Tensor, labels: torch.Tensor):
+    """The per-step classification metrics (metrics/metrics_base.py:157-160, 268-285) of one batch: logits (B, C)
+    f32 / bf16, labels (B,) int64 -> class_score's (result, counts, correct), bit-identical to class_append +
+    class_score of the same batch, without a buffer."""
+    B, C = _class_check("class_metrics", logits, labels)
+    K = _class_columns(C)
+    logits, labels = logits.detach().contiguous(), labels.contiguous()
+    _lib.require_gpu(logits, labels)
+    lib = _lib.load()
+    ws = torch.empty(lib.lci_class_metrics_ws_bytes(B, C), device=logits.device, dtype=torch.uint8)
+    counts, res = _class_out(K, logits.device)
+    KernelTimer.run("class_metrics", float(B) * B * K, logits, lambda: _lib.call(
+        "lci_class_metrics", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), counts.data_ptr(),
+        res.data_ptr(), ws.data_ptr(), B, C, _lib.stream_of(logits)))
+    return res, counts[:-1].view(K, 6), counts[-1]

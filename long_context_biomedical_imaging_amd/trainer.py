@@ -441,7 +441,7 @@ class GraphedStep:
 class EvalStep:
     """The reference's evaluation step (trainer_base.py:292-315): step(inputs, targets) runs the model in eval()
     under torch.inference_mode() and the trainer's bf16 autocast, computes the configured loss and scores the batch
-    into `self.metrics` (a metrics.TaskMetrics, sums kept on the device). Returns (output, loss), both device
+    into `self.metrics` (a metrics.TaskMetrics unless one is passed, sums kept on the device). Returns (output, loss), both device
     tensors: no host sync per step; `metrics.result()` is the one sync of an evaluation loop. Every module's training
     flag is restored afterwards, so a step can be interleaved with training.
 
@@ -450,13 +450,15 @@ class EvalStep:
     running statistics, which neither fails on one sample nor depends on the batch: the duplicate only doubles the
     work."""
 
-    def __init__(self, model, config, device):
+    def __init__(self, model, config, device, metrics=None):
+        """metrics: the metric manager to score into (metrics.build_metrics(config, "eval", capacity) for the
+        classification metrics); default a TaskMetrics(config)."""
         from .metrics import TaskMetrics
         self.device = device
         self.model = model
         self.loss_func = loss_fn(config)
         self.use_amp = bool(config.use_amp)
-        self.metrics = TaskMetrics(config)
+        self.metrics = TaskMetrics(config) if metrics is None else metrics
 
     def step(self, inputs, targets):
         flags = [(m, m.training) for m in self.model.modules()]
