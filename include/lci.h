@@ -9,6 +9,9 @@
  *     documented as "accumulated" must be zeroed by the caller.
  *   - dtype codes: 0 = f32, 1 = bf16 (IEEE bfloat16 stored as uint16). Row-major throughout.
  *   - "channels-last" = (B, L, C) with unit channel stride; "channel-major rows" = (rows, L).
+ *   - This header is the one declaration of the ABI: every definition in csrc/ is compiled against it, and the Python
+ *     binding reads its types from this text. Entry points return int, long long or const char* and take pointers,
+ *     int, float, double and long long only; the binding refuses a declaration it cannot type.
  *
  * Reference interfaces replaced (file:line under /root/reference)
  *   lci_attn_*            SABlock.forward attention core, model/models/backbone_vit.py:191-203

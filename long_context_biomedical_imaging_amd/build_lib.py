@@ -63,11 +63,13 @@ def _obj(src):
 
 
 def _obj_key(src, full_hash):
-    """Per-object content key: the source, the shared headers and the flags (abi.cpp also embeds the full hash)."""
+    """Per-object content key: the source, the shared headers, the public header every source is compiled against,
+    and the flags (abi.cpp also embeds the full hash)."""
     h = hashlib.sha256(_read(src))
     for f in sorted(os.listdir(CSRC)):
         if f.endswith(".hpp"):
             h.update(_read(os.path.join(CSRC, f)))
+    h.update(_read(HEADER))
     h.update(repr((FLAGS, DEVICE_FLAGS, FILE_FLAGS.get(os.path.basename(src)))).encode())
     if os.path.basename(src) == "abi.cpp":
         h.update(full_hash.encode())

@@ -6,6 +6,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The C ABI: every extern "C" definition is compiled against its public declaration. By relative path, so a tool that
+// compiles one source with build_lib.FLAGS alone (the ISA tests) needs no include directory.
+#include "../../include/lci.h"
+
 namespace lci {
 
 typedef __bf16 bf16;

@@ -158,7 +158,7 @@ def attn_gen_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
     out = torch.empty(B, L, num_heads * dh, device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(B, num_heads, L, device=qkv.device, dtype=torch.float32)
     KernelTimer.run("attn_gen_fwd", 4.0 * B * num_heads * L * L * dh, qkv, lambda: _lib.call(
-        "lci_attn_gen_fwd", _DT[qkv.dtype], qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, num_heads, dh,
+        "lci_attn_gen_fwd", _lib.DTYPE[qkv.dtype], qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), B, L, num_heads, dh,
         float(scale), _lib.stream_of(qkv)))
     return out, lse
 
@@ -170,7 +170,7 @@ def attn_gen_bwd(qkv, out, dout, lse, num_heads: int, scale: float):
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B, num_heads, L, device=qkv.device, dtype=torch.float32)
     KernelTimer.run("attn_gen_bwd", 8.0 * B * num_heads * L * L * dh, qkv, lambda: _lib.call(
-        "lci_attn_gen_bwd", _DT[qkv.dtype], qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
+        "lci_attn_gen_bwd", _lib.DTYPE[qkv.dtype], qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse.data_ptr(),
         dqkv.data_ptr(), delta.data_ptr(), B, L, num_heads, dh, float(scale), _lib.stream_of(qkv)))
     return dqkv
 
@@ -240,14 +240,6 @@ def flash_attention(qkv: torch.Tensor, num_heads: int, scale: float) -> torch.Te
 
 
 # ------------------------------------------------------------------------------------- patch embed
-_DT = {torch.float32: 0, torch.bfloat16: 1}
-
-
-def _i32arr(vals):
-    import ctypes
-    return (ctypes.c_int * 3)(*(list(vals) + [1] * (3 - len(vals))))
-
-
 class _PatchEmbed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, pos, channels_last, out_dtype):
@@ -263,9 +255,9 @@ class _PatchEmbed(torch.autograd.Function):
         wf = w.float().contiguous()
         bf = bias.float().contiguous() if bias is not None else None
         pf = pos.float().reshape(L, D).contiguous() if pos is not None else None
-        _lib.call("lci_patch_embed_fwd", x.data_ptr(), _DT[x.dtype], wf.data_ptr(), _lib.ptr(bf), _lib.ptr(pf),
-                  y.data_ptr(), _DT[out_dtype], B, C, D, len(S), _i32arr(S), _i32arr(P), int(channels_last),
-                  _lib.stream_of(x))
+        _lib.call("lci_patch_embed_fwd", x.data_ptr(), _lib.DTYPE[x.dtype], wf.data_ptr(), _lib.ptr(bf), _lib.ptr(pf),
+                  y.data_ptr(), _lib.DTYPE[out_dtype], B, C, D, len(S), _lib.c_array(ctypes.c_int, S, 3, 1),
+                  _lib.c_array(ctypes.c_int, P, 3, 1), int(channels_last), _lib.stream_of(x))
         ctx.save_for_backward(x)
         ctx.meta = (B, C, D, S, P, L, channels_last, w.shape, w.dtype, bias is not None, pos is not None,
                     pos.shape if pos is not None else None)
@@ -276,14 +268,14 @@ class _PatchEmbed(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         B, C, D, S, P, L, cl, wshape, wdtype, has_b, has_p, pshape = ctx.meta
         dy = dy.contiguous()
-        if dy.dtype not in _DT:
+        if dy.dtype not in _lib.DTYPE:
             dy = dy.float()
         dw = torch.zeros(wshape, device=x.device, dtype=torch.float32)
         db = torch.zeros(D, device=x.device, dtype=torch.float32) if has_b else None
         dpos = torch.empty(pshape, device=x.device, dtype=torch.float32) if has_p else None
-        _lib.call("lci_patch_embed_bwd", x.data_ptr(), _DT[x.dtype], dy.data_ptr(), _DT[dy.dtype], dw.data_ptr(),
-                  _lib.ptr(db), _lib.ptr(dpos), B, C, D, len(S), _i32arr(S), _i32arr(P), int(cl),
-                  _lib.stream_of(x))
+        _lib.call("lci_patch_embed_bwd", x.data_ptr(), _lib.DTYPE[x.dtype], dy.data_ptr(), _lib.DTYPE[dy.dtype],
+                  dw.data_ptr(), _lib.ptr(db), _lib.ptr(dpos), B, C, D, len(S), _lib.c_array(ctypes.c_int, S, 3, 1),
+                  _lib.c_array(ctypes.c_int, P, 3, 1), int(cl), _lib.stream_of(x))
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("patch_embed: gradient w.r.t. the input image is not provided")
         return None, dw.to(wdtype), (db if has_b else None), dpos, None, None
@@ -298,13 +290,13 @@ def patch_embed(x, weight, bias, pos, channels_last_tokens: bool):
     """
     _lib.require_gpu(x.contiguous())
     x = x.contiguous()
-    if x.dtype not in _DT:
+    if x.dtype not in _lib.DTYPE:
         x = x.float()
     if channels_last_tokens:
         out_dtype = torch.float32
     else:
         out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.float32
-        if out_dtype not in _DT:
+        if out_dtype not in _lib.DTYPE:
             out_dtype = torch.float32
     return _PatchEmbed.apply(x, weight, bias, pos, channels_last_tokens, out_dtype)
 
@@ -312,11 +304,6 @@ def patch_embed(x, weight, bias, pos, channels_last_tokens: bool):
 # ----------------------------------------------------------------------------------------- mamba
 SCAN_N = 8
 CKPT = 8          # = csrc/mamba.hip CKPT (backward checkpoint spacing)
-
-
-def _ll_array(vals):
-    import ctypes
-    return (ctypes.c_longlong * len(vals))(*vals)
 
 
 def _scan_chunk(L, B=1, Dx=64):
@@ -344,8 +331,8 @@ class _DWConvSiLUPair(torch.autograd.Function):
         w = [t.float().reshape(C, -1).contiguous() if t is not None else None for t in (wx, bx, wz, bz)]
         K = w[0].shape[1]
         KernelTimer.run("dwconv_silu_fwd", 0.0, xz, lambda: _lib.call(
-            "lci_dwconv_silu_fwd", _DT[xz.dtype], xz.data_ptr(), w[0].data_ptr(), _lib.ptr(w[1]), w[2].data_ptr(),
-            _lib.ptr(w[3]), xs.data_ptr(), yz.data_ptr(), B, L, C, K, C2, C, C2, C, _lib.stream_of(xz)))
+            "lci_dwconv_silu_fwd", _lib.DTYPE[xz.dtype], xz.data_ptr(), w[0].data_ptr(), _lib.ptr(w[1]),
+            w[2].data_ptr(), _lib.ptr(w[3]), xs.data_ptr(), yz.data_ptr(), B, L, C, K, C2, C, C2, C, _lib.stream_of(xz)))
         ctx.save_for_backward(xz, *[t for t in w if t is not None])
         ctx.meta = (bx is not None, bz is not None, wx.shape, wz.shape)
         return xs, yz
@@ -367,7 +354,7 @@ class _DWConvSiLUPair(torch.autograd.Function):
         rows = int(_lib.load().lci_dwconv_silu_bwd_part_rows(B, L))
         part = torch.empty(rows, 2 * C, 4, device=xz.device, dtype=torch.float32)
         KernelTimer.run("dwconv_silu_bwd", 0.0, xz, lambda: _lib.call(
-            "lci_dwconv_silu_bwd", _DT[xz.dtype], xz.data_ptr(), wx.data_ptr(), _lib.ptr(bx), wz.data_ptr(),
+            "lci_dwconv_silu_bwd", _lib.DTYPE[xz.dtype], xz.data_ptr(), wx.data_ptr(), _lib.ptr(bx), wz.data_ptr(),
             _lib.ptr(bz), gxs.data_ptr(), gyz.data_ptr(), din.data_ptr(), part.data_ptr(), B, L, C, K, C2, C, C2, C,
             _lib.stream_of(xz)))
         g = part.sum(0)                      # (2C, 4): dw0, dw1, dw2, db per channel (deterministic order)
@@ -384,7 +371,7 @@ def dwconv_silu_pair(xz, wx, bx, wz, bz):
     the first half of yz is left for the selective scan to fill (the reference's cat([y, z]), :136).
     """
     _lib.require_gpu(xz)
-    if xz.dtype not in _DT:
+    if xz.dtype not in _lib.DTYPE:
         xz = xz.float()
     xs, yz = _DWConvSiLUPair.apply(xz, wx, bx, wz, bz)
     yz._lci_z_half_only = True   # its backward reads only the z half of yz's gradient (see selective_scan_cl)
@@ -417,10 +404,10 @@ class _SelectiveScanCL(torch.autograd.Function):
         Dv = D.float().contiguous() if D is not None else torch.zeros(Dx, **f32)
         bv = delta_bias.float().contiguous() if delta_bias is not None else torch.zeros(Dx, **f32)
         y = yz[..., :Dx]
-        strides = _ll_array([*_bt(u), *_bt(delta), *_bt(Bm), *_bt(Cm), *_bt(y), 0, 0, 0, 0, 0, 0])
+        strides = _lib.c_array(ctypes.c_longlong, [*_bt(u), *_bt(delta), *_bt(Bm), *_bt(Cm), *_bt(y), 0, 0, 0, 0, 0, 0])
         es = u.element_size()   # algorithmic bytes: read u, delta, B, C; write y
         KernelTimer.run("selective_scan_fwd", float(B * L * (3 * Dx + 2 * N) * es), u, lambda: _lib.call(
-            "lci_selective_scan_fwd", _DT[dt], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
+            "lci_selective_scan_fwd", _lib.DTYPE[dt], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
             Cm.data_ptr(), Dv.data_ptr(), bv.data_ptr(), y.data_ptr(), strides, B, L, Dx, N, tc, int(softplus),
             _lib.ptr(xend), _lib.ptr(xinit), _lib.ptr(sdt), _lib.ptr(ckpt), _lib.stream_of(u)))
         ctx.mark_dirty(yz)
@@ -457,10 +444,11 @@ class _SelectiveScanCL(torch.autograd.Function):
         db = torch.zeros(Dx, **f32)
         gl = torch.empty(B, nch, Dx, N, **f32)
         gin = torch.empty(B, nch, Dx, N, **f32)
-        strides = _ll_array([*_bt(u), *_bt(delta), *_bt(Bm), *_bt(Cm), 0, 0, *_bt(dy), *_bt(du), *_bt(dd)])
+        strides = _lib.c_array(ctypes.c_longlong,
+                               [*_bt(u), *_bt(delta), *_bt(Bm), *_bt(Cm), 0, 0, *_bt(dy), *_bt(du), *_bt(dd)])
         es = u.element_size()   # read u, delta, dy, B, C; write du, ddelta, dB, dC
         KernelTimer.run("selective_scan_bwd", float(B * L * (5 * Dx + 4 * N) * es), u, lambda: _lib.call(
-            "lci_selective_scan_bwd", _DT[u.dtype], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
+            "lci_selective_scan_bwd", _lib.DTYPE[u.dtype], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
             Cm.data_ptr(), Dv.data_ptr(), bv.data_ptr(), dy.data_ptr(), du.data_ptr(), dd.data_ptr(),
             dBC.data_ptr(), dA.data_ptr(), dD.data_ptr(), db.data_ptr(), strides, B, L, Dx, N, tc,
             int(ctx.softplus), _lib.ptr(sdt), ckpt.data_ptr(), gl.data_ptr(), gin.data_ptr(), _lib.stream_of(u)))
@@ -486,7 +474,7 @@ def selective_scan_cl(u, delta, A, Bm, Cm, D, delta_bias, yz, delta_softplus=Tru
     """
     _lib.require_gpu(u, delta, yz)
     dt = u.dtype
-    if dt not in _DT:
+    if dt not in _lib.DTYPE:
         raise _lib.LciError("selective_scan: u must be bf16 or f32")
     u = u.contiguous()
     delta = delta.to(dt)
@@ -511,8 +499,7 @@ _MP_IDX = {}
 
 
 def _mp_dims(Dx, R, N2):
-    import ctypes
-    d = (ctypes.c_int * 5)()
+    d = _lib.c_array(ctypes.c_int, [], 5)
     _lib.call("lci_mamba_proj_dims", Dx, R, N2, d)
     return tuple(int(v) for v in d)
 
@@ -629,8 +616,8 @@ def mamba_proj(xs, Wx, Wdt, bias, R, N2, with_u=False):
 
 # ------------------------------------------------------------------------------------ window attention
 def _i32(vals):
-    import ctypes
-    return (ctypes.c_int * len(vals))(*[int(v) for v in vals])
+    """The int geo[16] argument (the window kernel tests build it through this name too)."""
+    return _lib.c_array(ctypes.c_int, vals)
 
 
 def _window_bias(rpb, mask, geo, transposed=False, plain=True):
@@ -725,8 +712,8 @@ def window_index_map(B, S, window_size, shift_size, device="cuda"):
     i32 = dict(device=device, dtype=torch.int32)
     src, reg, rid = (torch.empty(Bw, N, **i32) for _ in range(3))
     wt = torch.empty(Bw, **i32)
-    _lib.call("lci_window_index_map", _i32(geo), src.data_ptr(), reg.data_ptr(), rid.data_ptr(), wt.data_ptr(),
-              torch.cuda.current_stream(torch.device(device)).cuda_stream)
+    _lib.call("lci_window_index_map", _i32(geo), src.data_ptr(), reg.data_ptr(), rid.data_ptr(),
+              wt.data_ptr(), torch.cuda.current_stream(torch.device(device)).cuda_stream)
     return src, reg, rid, wt
 
 
@@ -760,8 +747,8 @@ def window_attention_grid(qkv, bias, rpb, num_heads, scale, window_size, shift_s
 
 
 def _win_move(src, dst, geo, scatter):
-    _lib.call("lci_window_gather", src.data_ptr(), dst.data_ptr(), src.element_size(), _i32(geo), int(scatter),
-              _lib.stream_of(src))
+    _lib.call("lci_window_gather", src.data_ptr(), dst.data_ptr(), src.element_size(), _i32(geo),
+              int(scatter), _lib.stream_of(src))
 
 
 class _WindowGather(torch.autograd.Function):
@@ -1005,7 +992,7 @@ class _HyenaPre(torch.autograd.Function):
         vg = torch.empty(BB, D, L, device=z.device, dtype=torch.float32)
         x2 = torch.empty(BB, L, D, device=z.device, dtype=z.dtype)
         KernelTimer.run("hyena_pre_fwd", 0.0, z, lambda: _lib.call(
-            "lci_hyena_pre_fwd", _DT[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), vg.data_ptr(),
+            "lci_hyena_pre_fwd", _lib.DTYPE[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), vg.data_ptr(),
             x2.data_ptr(), BB, L, num_heads, hd, K, _lib.stream_of(z)))
         ctx.save_for_backward(z, wf, bf)
         ctx.meta = (num_heads, w.shape, b is not None)
@@ -1028,7 +1015,7 @@ class _HyenaPre(torch.autograd.Function):
         dw = torch.zeros(C3, K, **f32)
         db = torch.zeros(C3, **f32) if has_b else None
         KernelTimer.run("hyena_pre_bwd", 0.0, z, lambda: _lib.call(
-            "lci_hyena_pre_bwd", _DT[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), dvg.data_ptr(),
+            "lci_hyena_pre_bwd", _lib.DTYPE[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), dvg.data_ptr(),
             dx2.data_ptr(), dz.data_ptr(), dw.data_ptr(), _lib.ptr(db), BB, L, num_heads, hd, K, _lib.stream_of(z)))
         return dz, dw.reshape(wshape), db, None
 
@@ -1039,7 +1026,7 @@ class _HyenaPost(torch.autograd.Function):
         BB, D, L = y.shape
         out = torch.empty(BB, L, D, device=y.device, dtype=x2.dtype)
         KernelTimer.run("hyena_post_fwd", 0.0, y, lambda: _lib.call(
-            "lci_hyena_post_fwd", _DT[x2.dtype], y.data_ptr(), x2.data_ptr(), out.data_ptr(), BB, L, D,
+            "lci_hyena_post_fwd", _lib.DTYPE[x2.dtype], y.data_ptr(), x2.data_ptr(), out.data_ptr(), BB, L, D,
             _lib.stream_of(y)))
         ctx.save_for_backward(y, x2)
         return out
@@ -1052,7 +1039,7 @@ class _HyenaPost(torch.autograd.Function):
         dy = torch.empty(BB, D, L, device=y.device, dtype=torch.float32)
         dx2 = torch.empty(BB, L, D, device=y.device, dtype=x2.dtype)   # x2's dtype: the engine casts nothing
         KernelTimer.run("hyena_post_bwd", 0.0, y, lambda: _lib.call(
-            "lci_hyena_post_bwd", _DT[x2.dtype], y.data_ptr(), x2.data_ptr(), dout.data_ptr(), dy.data_ptr(),
+            "lci_hyena_post_bwd", _lib.DTYPE[x2.dtype], y.data_ptr(), x2.data_ptr(), dout.data_ptr(), dy.data_ptr(),
             dx2.data_ptr(), BB, L, D, _lib.stream_of(y)))
         return dy, dx2
 
@@ -1064,7 +1051,7 @@ def hyena_pre(z, weight, bias, num_heads):
     """
     _lib.require_gpu(z.contiguous())
     z = z.contiguous()
-    if z.dtype not in _DT:
+    if z.dtype not in _lib.DTYPE:
         z = z.float()
     return _HyenaPre.apply(z, weight, bias, num_heads)
 
@@ -2305,7 +2292,7 @@ def _sched_array(sched):
     if len(vals) != 7:
         raise _lib.LciError("one-cycle schedule: (total_steps, end_step1, initial_lr, max_lr, min_lr, base_momentum, "
                             "max_momentum) expected")
-    return (ctypes.c_double * 8)(*vals, 0.0)
+    return _lib.c_array(ctypes.c_double, vals, 8)
 
 
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1: float, beta2: float,
@@ -2337,8 +2324,8 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr: float, beta1: flo
     for i0 in range(0, len(params), per):
         sl = slice(i0, i0 + per)
         n = len(params[sl])
-        arr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])   # noqa: E731
-        sizes = (ctypes.c_longlong * n)(*[t.numel() for t in params[sl]])
+        arr = lambda ts: _lib.c_array(ctypes.c_void_p, [t.data_ptr() for t in ts])   # noqa: E731
+        sizes = _lib.c_array(ctypes.c_longlong, [t.numel() for t in params[sl]])
         args = (arr(params[sl]), arr(grads[sl]), arr(exp_avgs[sl]), arr(exp_avg_sqs[sl]),
                 arr(steps[sl]), sizes, n, float(lr), float(beta1), float(beta2), float(weight_decay), float(eps),
                 int(decoupled), int(maximize))
@@ -2379,8 +2366,8 @@ def grad_clip_coef(grads, max_norm: float):
     for i0 in range(0, len(grads), per):
         gs = grads[i0:i0 + per]
         n = len(gs)
-        sizes = (ctypes.c_longlong * n)(*[t.numel() for t in gs])
-        calls.append(((ctypes.c_void_p * n)(*[t.data_ptr() for t in gs]), sizes, n, total))
+        sizes = _lib.c_array(ctypes.c_longlong, [t.numel() for t in gs])
+        calls.append((_lib.c_array(ctypes.c_void_p, [t.data_ptr() for t in gs]), sizes, n, total))
         total += lib.lci_grad_sumsq_parts(sizes, n)
     part = torch.empty(max(1, total), device=dev, dtype=torch.float64)
     out = torch.empty(2, device=dev, dtype=torch.float32)
@@ -2402,7 +2389,7 @@ class _EnhanceLoss(torch.autograd.Function):
         ws = torch.empty(max(16, lib.lci_enhance_loss_ws_bytes(B, T, H, W)), device=outputs.device, dtype=torch.uint8)
         grad = torch.empty_like(outputs)
         res = torch.empty(4, device=outputs.device, dtype=torch.float32)
-        code = {torch.float32: 0, torch.bfloat16: 1}
+        code = _lib.DTYPE
         elems = outputs.numel()
         traffic = float(elems * (2 * outputs.element_size() + targets.element_size()))
         KernelTimer.run("enhance_loss", traffic, outputs, lambda: _lib.call(
@@ -2447,7 +2434,6 @@ def enhance_loss(outputs: torch.Tensor, targets: torch.Tensor, taps: torch.Tenso
 
 # ------------------------------------------------------------------------------------------- task metrics
 SSIM_TILE = (6, 16, 32)   # interior (T, H, W) extents one workgroup of csrc/metrics.hip covers (lci_ssim_tile); 2-D: H, W
-_METRIC_DTYPES = {torch.float32: 0, torch.bfloat16: 1}
 
 
 def enhance_metrics(outputs: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
@@ -2460,7 +2446,7 @@ def enhance_metrics(outputs: torch.Tensor, targets: torch.Tensor) -> torch.Tenso
         raise ValueError(f"enhance_metrics: outputs {tuple(outputs.shape)} and targets {tuple(targets.shape)} must "
                          "be the same (B, C, T, H, W) shape")
     for t in (outputs, targets):
-        if t.dtype not in _METRIC_DTYPES:
+        if t.dtype not in _lib.DTYPE:
             raise ValueError(f"enhance_metrics: dtype {t.dtype} (f32 or bf16 only)")
     B, C, T, H, W = outputs.shape
     if min(B, C, T) < 1:
@@ -2478,8 +2464,8 @@ def enhance_metrics(outputs: torch.Tensor, targets: torch.Tensor) -> torch.Tenso
     # both tensors are read by the statistics pass and again by the window pass
     traffic = float(2 * outputs.numel() * (outputs.element_size() + targets.element_size()))
     KernelTimer.run("enhance_metrics", traffic, outputs, lambda: _lib.call(
-        "lci_enhance_metrics", outputs.data_ptr(), _METRIC_DTYPES[outputs.dtype], targets.data_ptr(),
-        _METRIC_DTYPES[targets.dtype], res.data_ptr(), ws.data_ptr(), B, C, T, H, W, _lib.stream_of(outputs)))
+        "lci_enhance_metrics", outputs.data_ptr(), _lib.DTYPE[outputs.dtype], targets.data_ptr(),
+        _lib.DTYPE[targets.dtype], res.data_ptr(), ws.data_ptr(), B, C, T, H, W, _lib.stream_of(outputs)))
     return res
 
 
@@ -2496,7 +2482,7 @@ def seg_f1(logits: torch.Tensor, labels: torch.Tensor):
     B, C = logits.shape[:2]
     if not 2 <= C <= 64:
         raise ValueError(f"seg_f1: C = {C} outside [2, 64]")
-    if logits.dtype not in _METRIC_DTYPES:
+    if logits.dtype not in _lib.DTYPE:
         raise ValueError(f"seg_f1: logits dtype {logits.dtype} (f32 or bf16 only)")
     if labels.dtype != torch.int64:
         raise ValueError(f"seg_f1: labels dtype {labels.dtype} (int64 only)")
@@ -2511,7 +2497,7 @@ def seg_f1(logits: torch.Tensor, labels: torch.Tensor):
     res = torch.empty(1, device=logits.device, dtype=torch.float32)
     traffic = float(logits.numel() * logits.element_size() + labels.numel() * 8)
     KernelTimer.run("seg_f1", traffic, logits, lambda: _lib.call(
-        "lci_seg_f1", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), counts.data_ptr(),
+        "lci_seg_f1", logits.data_ptr(), _lib.DTYPE[logits.dtype], labels.data_ptr(), counts.data_ptr(),
         res.data_ptr(), ws.data_ptr(), B, C, S, _lib.stream_of(logits)))
     return res[0], counts
 
@@ -2526,7 +2512,7 @@ def _class_check(name, logits, labels):
     B, C = logits.shape
     if not 2 <= C <= 64:
         raise ValueError(f"{name}: C = {C} outside [2, 64]")
-    if logits.dtype not in _METRIC_DTYPES:
+    if logits.dtype not in _lib.DTYPE:
         raise ValueError(f"{name}: logits dtype {logits.dtype} (f32 or bf16 only)")
     if labels.dtype != torch.int64:
         raise ValueError(f"{name}: labels dtype {labels.dtype} (int64 only)")
@@ -2565,7 +2551,7 @@ def class_append(logits: torch.Tensor, labels: torch.Tensor, probs: torch.Tensor
     _lib.require_gpu(logits, labels, probs, label_buf, count)
     traffic = float(logits.numel() * logits.element_size() + B * (8 + 8 + 4 * K))
     KernelTimer.run("class_append", traffic, logits, lambda: _lib.call(
-        "lci_class_append", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), probs.data_ptr(),
+        "lci_class_append", logits.data_ptr(), _lib.DTYPE[logits.dtype], labels.data_ptr(), probs.data_ptr(),
         label_buf.data_ptr(), count.data_ptr(), probs.shape[0], B, C, _lib.stream_of(logits)))
 
 
@@ -2605,6 +2591,6 @@ def class_metrics(logits: torch.Tensor, labels: torch.Tensor):
     ws = torch.empty(lib.lci_class_metrics_ws_bytes(B, C), device=logits.device, dtype=torch.uint8)
     counts, res = _class_out(K, logits.device)
     KernelTimer.run("class_metrics", float(B) * B * K, logits, lambda: _lib.call(
-        "lci_class_metrics", logits.data_ptr(), _METRIC_DTYPES[logits.dtype], labels.data_ptr(), counts.data_ptr(),
+        "lci_class_metrics", logits.data_ptr(), _lib.DTYPE[logits.dtype], labels.data_ptr(), counts.data_ptr(),
         res.data_ptr(), ws.data_ptr(), B, C, _lib.stream_of(logits)))
     return res, counts[:-1].view(K, 6), counts[-1]

@@ -1,5 +1,6 @@
 """The C-ABI library loads on CPU-only hosts and exports every symbol include/lci.h declares; the Python
-binding's argument lists match the header's (no compute calls: there is no GPU here)."""
+binding, which derives every restype / argtypes from that header, agrees with this file's own reading of it and with
+a literal table of full types (no compute calls: there is no GPU here)."""
 import ctypes
 import os
 import re
@@ -56,11 +57,66 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_python_binding_arity_matches_header():
+    """The binding's reader and this file's agree on the set of declared functions and on every argument count."""
     from long_context_biomedical_imaging_amd import _lib
     d = _declared()
-    for name, argt in _lib.SIGNATURES.items():
-        assert name in d, f"{name} bound in Python but not declared"
+    sigs = _lib.signatures(open(HDR).read())
+    assert sorted(sigs) == sorted(d)
+    assert _lib.header() == (_header_abi_version(), sigs)
+    for name, (_, argt) in sigs.items():
         assert len(argt) == len(d[name]), f"{name}: python {len(argt)} args, header {len(d[name])}"
+
+
+P, I, F, D, L = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_longlong
+EXPECTED = {   # every scalar type, both non-status returns, no arguments, arrays as pointers
+    "lci_attn_fwd": (I, [P, P, P, P, I, I, I, I, F, P]),
+    "lci_adam_step": (I, [P, P, P, P, P, P, I, D, D, D, D, D, I, I, P]),
+    "lci_inorm_reduce": (I, [P, P, P, P, L, I, I, I, F, P]),
+    "lci_attn_fwd_ws_bytes": (L, [I, I, I]),
+    "lci_last_error": (ctypes.c_char_p, []),
+    "lci_linear_small_threads": (I, []),
+    "lci_patch_embed_fwd": (I, [P, I, P, P, P, P, I, I, I, I, I, P, P, I, P]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(EXPECTED))
+def test_python_binding_types_match_literal_table(name):
+    from long_context_biomedical_imaging_amd import _lib
+    assert _lib.header()[1][name] == EXPECTED[name]
+
+
+def test_binding_reader_types_each_shape():
+    from long_context_biomedical_imaging_amd import _lib
+    sigs = _lib.signatures("/* int lci_no(int a); */\nconst char *lci_s(void);\nlong long lci_n(const int geo[16], "
+                           "float* const* p,\n   double x, long long n);")
+    assert sigs == {"lci_s": (ctypes.c_char_p, []), "lci_n": (L, [P, P, D, L])}
+
+
+@pytest.mark.parametrize("text", ["int lci_f(unsigned x);", "int lci_f(int a, unsigned long n, void* stream);",
+                                  "unsigned lci_f(int a);", "float lci_f(int a);", "int lci_f(int);",
+                                  "typedef int lci_t;"])
+def test_binding_reader_refuses_what_it_cannot_type(text):
+    from long_context_biomedical_imaging_amd import _lib
+    with pytest.raises(_lib.LciError, match="lci_"):
+        _lib.signatures("int lci_ok(int a);\n" + text)
+
+
+def test_missing_header_is_an_error(monkeypatch, tmp_path):
+    from long_context_biomedical_imaging_amd import _lib, build_lib
+    monkeypatch.setattr(build_lib, "HEADER", str(tmp_path / "lci.h"))
+    with pytest.raises(_lib.LciError, match="lci.h"):
+        _lib.header.__wrapped__()
+
+
+def test_loaded_library_has_every_function_typed():
+    from long_context_biomedical_imaging_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("liblci.so not built (python -m long_context_biomedical_imaging_amd.build_lib)")
+    lib = _lib.load()
+    for name, (restype, argtypes) in _lib.header()[1].items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name} left untyped"
+        assert (fn.restype, list(fn.argtypes)) == (restype, argtypes), name
 
 
 def test_integration_doc_stubs_match_header():

@@ -162,11 +162,10 @@ def bench_other_lib(name, workload, other, rounds, iters, emit, dev):
     (the order swaps every round). The C entry point is called directly, so the binding's ABI check does not apply."""
     import ctypes
     from long_context_biomedical_imaging_amd import _lib
-    P, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    P = ctypes.c_void_p
     libs = {"other": ctypes.CDLL(os.path.abspath(other)), "this": ctypes.CDLL(_lib.DEFAULT_LIB)}
     for lib in libs.values():
-        lib.lci_adam_step.argtypes = [P, P, P, P, P, P, I, D, D, D, D, D, I, I, P]
-        lib.lci_adam_step.restype = I
+        _lib.bind(lib, ["lci_adam_step"])
     shapes = param_shapes(workload)
     g = torch.Generator(device=dev).manual_seed(3)
     p = [torch.randn(s, device=dev, generator=g) * 0.02 for s in shapes]
