@@ -52,6 +52,8 @@
  *                         _ex also evaluates the recipes' OneCycleLR (optim_base.py:113-115, stepped at
  *                         trainer_base.py:181-182) from the device step count, or reads a device learning rate
  *   lci_grad_sumsq/_clip_coef  nn.utils.clip_grad_norm_'s norm and coefficient (trainer_base.py:173-175)
+ *   lci_augment           the per-voxel work of the training transforms of define_transforms (data/data_utils.py:120-150,
+ *                         data/augmentation_functions/brightness.py), from parameters drawn on the host
  */
 #ifndef LCI_H_
 #define LCI_H_
@@ -76,8 +78,9 @@ extern "C" {
  * lci_selective_scan_bwd_plain_dbc); 33: lci_gemm_bt_small (+ _supported, _acc); 34: lci_enhance_loss (+ _ws_bytes);
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
  * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile;
- * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef. */
-#define LCI_ABI_VERSION 39
+ * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef; 39: lci_class_*;
+ * 40: lci_augment (+ _ws_bytes). */
+#define LCI_ABI_VERSION 40
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -621,6 +624,39 @@ int lci_class_score(const float* probs, const long long* labels, long long* coun
                     int C, void* stream);
 int lci_class_metrics(const void* logits, int dtype, const long long* labels, long long* counts, double* result,
                       void* ws, int B, int C, void* stream);
+
+/* ------------------------------------------------------------------ training augmentation (csrc/augment.hip)
+ * The recipes' RandomAffine (nearest, zero fill), RandomBrightnessContrast and GaussianBlur(kernel_size=(1, 3)) of
+ * data/data_utils.py:120-150 applied to one tensor of a batch from parameters the host drew (data.draw_params), one
+ * record of 16 f32 per sample in device memory. A restatement of torchvision 0.16.1's published algorithms, as
+ * data.py is; it was not compared with torchvision itself.
+ *   x, y : (B, P, H, W) contiguous, P = C T, out of place (y must not overlap x); dtype code 0 = f32 or, for this
+ *          entry point only, 2 = int64. P H W < 2^31, B <= 65535; batch offsets are 64-bit.
+ *   params : (B, 16) f32, field indices (data.AUG_*):
+ *      0      affine_on   0 or 1
+ *      1..6   m[0..5]     inverse affine matrix in pixel units about the centre, row-major 2 x 3
+ *      7      bc_on       0 or 1
+ *      8, 9   alpha, beta contrast factor, brightness factor
+ *      10     blur_on     0 or 1
+ *      11..13 taps[0..2]  the three taps along H
+ *      14, 15 zero
+ *   Per sample, with w the warped sample, all of it in that order:
+ *     affine: output pixel (i, j) of every plane takes x at (iy, ix) = (rne(sy), rne(sx)),
+ *        sx = m0 xc + m1 yc + m2 + (W - 1) / 2, sy = m3 xc + m4 yc + m5 + (H - 1) / 2, xc = j - W / 2 + 1/2,
+ *        yc = i - H / 2 + 1/2, evaluated in f64 and rounded to nearest, ties to even; 0 when (iy, ix) is outside the
+ *        plane (or a coordinate is NaN). affine_on = 0: w = x, bit for bit.
+ *     brightness: b = alpha w + beta mean(alpha w), the mean over all P H W values of the sample (products rounded to
+ *        f32, summed in f64, the mean rounded to f32). bc_on = 0: b = w, bit for bit.
+ *     blur: y(i) = taps[0] b(i - 1) + taps[1] b(i) + taps[2] b(i + 1) along H, reflect padding (b(-1) = b(1),
+ *        b(H) = b(H - 2)); needs H >= 2. blur_on = 0: y = b.
+ *   int64 takes the affine only; the other fields are ignored and H may be 1.
+ *   ws: lci_augment_ws_bytes(B, P, H, W) bytes (-1 for a bad shape), 16-byte aligned: per-workgroup partial sums of
+ *   the mean, re-added in a fixed order by every workgroup of the second pass. No atomics (bitwise reproducible from
+ *   call to call), no host sync; every parameter is read from device memory, so a captured call follows new
+ *   parameters on replay. x, y 16-byte aligned take 16-byte stores when W is a multiple of 4 (f32) or 2 (int64). */
+long long lci_augment_ws_bytes(int B, int P, int H, int W);
+int lci_augment(const void* x, void* y, int dtype, const float* params, void* ws, int B, int P, int H, int W,
+                void* stream);
 
 #ifdef __cplusplus
 }

@@ -2594,3 +2594,52 @@ def class_metrics(logits: torch.Tensor, labels: torch.Tensor):
         "lci_class_metrics", logits.data_ptr(), _lib.DTYPE[logits.dtype], labels.data_ptr(), counts.data_ptr(),
         res.data_ptr(), ws.data_ptr(), B, C, _lib.stream_of(logits)))
     return res, counts[:-1].view(K, 6), counts[-1]
+
+
+# ------------------------------------------------------------------------------------ training augmentation
+AUG_FIELDS = 16    # csrc/augment.hip AUG_FIELDS: f32 per record (include/lci.h states the layout; data.AUG_*)
+AUG_DTYPE = {torch.float32: 0, torch.int64: 2}
+
+
+def augment(x: torch.Tensor, params: torch.Tensor, out: torch.Tensor | None = None, *,
+            bc_samples: int | None = None) -> torch.Tensor:
+    """The recipes' RandomAffine (nearest, zero fill), RandomBrightnessContrast and GaussianBlur((1, 3)) of one
+    batch tensor on csrc/augment.hip, from records drawn on the host (data.draw_params): x (B, P, H, W) contiguous
+    f32 or int64 (int64: the affine only), params (B, 16) f32 on x's device, one record per sample. Returns `out`
+    (x's shape and dtype, contiguous, not overlapping x; allocated when None). No host sync, bitwise reproducible,
+    and every parameter is read on the device, so a captured call follows new parameters on replay. bc_samples: how
+    many records have brightness on, where the caller knows it (they cost a second read of x); it only enters the
+    traffic figure KernelTimer reports."""
+    if x.dim() != 4:
+        raise ValueError(f"augment: x {tuple(x.shape)} must be (B, P, H, W)")
+    if x.dtype not in AUG_DTYPE:
+        raise ValueError(f"augment: x dtype {x.dtype} (f32 or int64 only)")
+    B, P, H, W = x.shape
+    if not 1 <= B <= 65535 or min(P, H, W) < 1:
+        raise ValueError(f"augment: x {tuple(x.shape)}: B in 1 .. 65535 and no empty axis")
+    if P * H * W >= 2 ** 31:
+        raise ValueError(f"augment: {P * H * W} elements per sample (below 2^31)")
+    if x.dtype == torch.float32 and H < 2:
+        raise ValueError(f"augment: H = {H}; the reflect-padded blur along H needs H >= 2")
+    if params.dtype != torch.float32 or tuple(params.shape) != (B, AUG_FIELDS):
+        raise ValueError(f"augment: params {tuple(params.shape)} {params.dtype} must be ({B}, {AUG_FIELDS}) f32")
+    if not x.is_contiguous() or not params.is_contiguous():
+        raise ValueError("augment: x and params must be contiguous")
+    if out is not None:
+        if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
+            raise ValueError(f"augment: out {tuple(out.shape)} {out.dtype} on {out.device} must match x "
+                             f"{tuple(x.shape)} {x.dtype} on {x.device}")
+        if not out.is_contiguous():
+            raise ValueError("augment: out must be contiguous")
+        if out.data_ptr() == x.data_ptr():
+            raise ValueError("augment: out must not be x (the op is out of place)")
+    _lib.require_gpu(x, params, out)
+    lib = _lib.load()
+    y = torch.empty_like(x) if out is None else out
+    ws = torch.empty(lib.lci_augment_ws_bytes(B, P, H, W), device=x.device, dtype=torch.uint8)
+    reads = 1.0 + (0.0 if x.dtype != torch.float32 or not bc_samples else float(bc_samples) / B)
+    traffic = float(x.numel() * x.element_size()) * (reads + 1.0)
+    KernelTimer.run("augment", traffic, x, lambda: _lib.call(
+        "lci_augment", x.data_ptr(), y.data_ptr(), AUG_DTYPE[x.dtype], params.data_ptr(), ws.data_ptr(), B, P, H, W,
+        _lib.stream_of(x)))
+    return y
