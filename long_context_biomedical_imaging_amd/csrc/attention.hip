@@ -211,6 +211,85 @@ template <class F, int... G>
 __device__ __forceinline__ void hs_for_gaps(F&& f, std::integer_sequence<int, G...>) {
   (f(std::integral_constant<int, G>{}), ...);
 }
+
+// ---- what the five placed kernels share. These helpers only compute values: where a kernel waits (hs_vmcnt) and
+// where it moves fragments to AGPRs (HS_TO_AGPR) is part of its measured build and stays written in the kernel. The
+// register allocation of a placed loop follows the order of the prologue's statements, down to independent ones, and
+// the form the compiler sees them in before inlining: a helper keeps the statements it replaced, in their order
+// (the thread decomposition, the fragment offsets and the forward's prologue and exact path moved registers or
+// streams when shared, and stay in the kernels; DESIGN.md "Attention: shared pieces").
+// The tile ring: 4 slots of two 64-row tiles (Q | dO or K | V, 128-B sw128 rows), tile t in slot t & 3. It fills
+// exactly 64 KB, so every fragment read of every slot is one lane register + a 16-bit DS immediate.
+constexpr int HS_TILE_B = KT * DH * 2;
+constexpr int HS_SLOT_B = 2 * HS_TILE_B;
+constexpr int HS_NSLOT = 4;
+static_assert((HS_NSLOT & (HS_NSLOT - 1)) == 0, "ring slot of tile t is t & (HS_NSLOT - 1)");
+static_assert(HS_NSLOT * HS_SLOT_B == 65536, "ring reachable by DS immediates");
+
+// A wave's share of staging a ring of (X | Y) tiles of a head: rows 16 wave .. 16 wave + 15 of each tile as two 1-KB
+// pieces of 8 rows (lane l -> row l >> 3 of the piece, physical 16-B chunk l & 7, fetched from the logical chunk
+// (l & 7) ^ g(row) of the sw128 swizzle). Operations 0-3 of a tile: X piece 0, 1, Y piece 0, 1. Rows >= L read as zero.
+struct HsRing {
+  rsrc_t rx, ry;
+  int x0, x1, y0, y1;   // the lane's byte offset within a tile, per operation
+  int rs2x, rs2y;       // row strides in bytes
+  unsigned lds0;        // LDS address of the ring
+  int wave;
+  // byte offset of tile t in its tensor: unsigned, tiles a few past the last are addressed (out of range: zeros) and
+  // the entry points bound (L + 6 KT) rows by 2^31 bytes
+  static __device__ __forceinline__ int toff(int t, int rs2) { return (int)((uint32_t)t * KT * (uint32_t)rs2); }
+  __device__ __forceinline__ rsrc_t rsrc(int i) const { return i < 2 ? rx : ry; }
+  __device__ __forceinline__ int voff(int i) const { return i == 0 ? x0 : i == 1 ? x1 : i == 2 ? y0 : y1; }
+  __device__ __forceinline__ int soff(int t, int i) const { return toff(t, i < 2 ? rs2x : rs2y); }
+  // operation i of tile t straight into the tile's ring slot by LDS-DMA (the prologue)
+  __device__ __forceinline__ void dma(int t, int i) const {
+    const unsigned sb = lds0 + (unsigned)((t & (HS_NSLOT - 1)) * HS_SLOT_B);
+    hs_dma16(rsrc(i), voff(i), soff(t, i), sb + (i >> 1) * HS_TILE_B + 2048 * wave + (i & 1) * 1024);
+  }
+};
+// buffer resource over rows 0 .. L-1 (DH bf16 each, row stride rs2 bytes) of a head's tensor
+__device__ __forceinline__ rsrc_t hs_rows_rsrc(const bf16* p, int rs2, int L) {
+  return make_rsrc(p, (uint32_t)(L - 1) * (uint32_t)rs2 + DH * 2);
+}
+// (the resources are the caller's, made in its own order: the dK/dV kernel makes its row-constant resource between)
+__device__ __forceinline__ HsRing hs_ring(rsrc_t rx, int rs2x, rsrc_t ry, int rs2y, int lane, int wave,
+                                          const char* smem) {
+  HsRing r;
+  r.rx = rx;
+  r.ry = ry;
+  r.rs2x = rs2x;
+  r.rs2y = rs2y;
+  // row = 16 wave + 8 j + prow (piece j = 0, 1): g(row) = ((row >> 2) & 3) | ((row >> 1) & 1) << 2 = (2j + (prow >> 2))
+  // | ((prow >> 1) & 1) << 2
+  const int prow = lane >> 3;
+  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
+  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
+  r.x0 = (16 * wave + prow) * r.rs2x + 16 * pch0, r.x1 = (16 * wave + 8 + prow) * r.rs2x + 16 * pch1;
+  r.y0 = (16 * wave + prow) * r.rs2y + 16 * pch0, r.y1 = (16 * wave + 8 + prow) * r.rs2y + 16 * pch1;
+  r.lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
+  r.wave = wave;
+  return r;
+}
+
+// B-operand fragments of the backward kernels' operand pairs (K | V or Q | dO), one 32-row block: xf[ks] / yf[ks] =
+// x / y[row][16 ks + 8 h .. + 7] of the head's tensors (row strides rs_x, rs_y), zeros for a row past L, x prescaled
+// by c into the exp2 domain and rounded to bf16 again. The caller waits for the loads (hs_vmcnt) and moves the
+// fragments to AGPRs where its own stream wants that.
+__device__ __forceinline__ void hs_load_b2(bf16x8 (&xf)[4], bf16x8 (&yf)[4], const bf16* xp, int rs_x, const bf16* yp,
+                                           int rs_y, int row, int L, int h, float c) {
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    if (row < L) {
+      xf[ks] = *(const bf16x8*)(xp + (long long)row * rs_x + 16 * ks + 8 * h);
+      yf[ks] = *(const bf16x8*)(yp + (long long)row * rs_y + 16 * ks + 8 * h);
+    } else {
+      xf[ks] = bf16x8{};
+      yf[ks] = bf16x8{};
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) xf[ks][j] = to_bf16(to_f32(xf[ks][j]) * c);
+  }
+}
 // Row constants of the next half by DPP (LCI_DKDV_DPPRC=1): one ds_read_b32 per constant row set (lane l holds the
 // constant of register l & 15 of its half-wave) and 16 v_mov_b32_dpp row_newbcast:i per set, instead of eight
 // broadcast 16-byte reads per half (a quarter of the kernel's LDS return bytes); the sets alternate with the halves.
@@ -242,17 +321,11 @@ __device__ __forceinline__ float hs_bcast_i(float x, int i) {   // (i compile-ti
 }
 __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArgs a) {
   constexpr bool DPPRC = LCI_DKDV_DPPRC != 0;
-  constexpr int TILE_B = KT * DH * 2;               // bytes of a Q or dO tile (128-B rows)
-  constexpr int SLOT_B = 2 * TILE_B;                // Q | dO of one tile
+  // the Q | dO ring: tile t, t+1 (published), t+2, t+3 (in flight); the row-constant rows follow in their own 2 KB
   constexpr int RC_B = 2 * KT * 4;                  // -lse2[64] | -delta[64] of one tile
-  constexpr int NSLOT = 4;                          // ring: tile t, t+1 (published), t+2, t+3 (in flight)
   constexpr int NOPS = 5;                           // LDS-DMA operations per wave and tile (prologue)
-  static_assert((NSLOT & (NSLOT - 1)) == 0, "ring slot of tile t is t & (NSLOT - 1)");
-  // the Q / dO ring fills exactly 64 KB, so every fragment read of every slot is one lane register + a 16-bit
-  // immediate (slot, dO and row offsets); the row-constant rows follow in their own 2 KB
-  static_assert(NSLOT * SLOT_B == 65536, "Q / dO ring reachable by DS immediates");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B + NSLOT * RC_B];
-  char* const rcs = smem + NSLOT * SLOT_B;
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B + HS_NSLOT * RC_B];
+  char* const rcs = smem + HS_NSLOT * HS_SLOT_B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hh = blockIdx.y, b = blockIdx.z;
@@ -268,19 +341,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
     const bf16* vp = a.v + b * a.bs_v + hh * a.hs;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      const int key = kw0 + 32 * kb + r32;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if (key < L) {
-          kf[kb][ks] = *(const bf16x8*)(kp + (long long)key * a.rs_k + 16 * ks + 8 * h);
-          vf[kb][ks] = *(const bf16x8*)(vp + (long long)key * a.rs_v + 16 * ks + 8 * h);
-        } else {
-          kf[kb][ks] = bf16x8{};
-          vf[kb][ks] = bf16x8{};
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) kf[kb][ks][j] = to_bf16(to_f32(kf[kb][ks][j]) * a.c);
-      }
+      hs_load_b2(kf[kb], vf[kb], kp, a.rs_k, vp, a.rs_v, kw0 + 32 * kb + r32, L, h, a.c);
     }
   }
   // the K / V loads complete here: otherwise the compiler waits for them (vmcnt(0)) at their first use inside the
@@ -292,30 +353,19 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
     for (int j = 0; j < 4; ++j)
       { HS_TO_AGPR(kf[i][j]); HS_TO_AGPR(vf[i][j]); }
 
-  // ---- prologue staging by LDS-DMA: wave w copies rows 16w .. 16w+15 of the Q and dO tiles as 1-KB pieces
-  // (8 rows x 128 B, lane l -> row l >> 3 of the piece, physical 16-B chunk l & 7, fetched from the logical chunk
-  // (l & 7) ^ g(row) of the sw128 swizzle), and one row of row constants (waves 0 / 2: -lse2, 1 / 3: -delta; the
-  // pairs write the same bytes). Rows >= L read as zero: they add nothing to dV or dK whatever P is.
+  // ---- prologue staging by LDS-DMA: the wave's pieces of the Q and dO tiles (HsRing), and one row of row
+  // constants (waves 0 / 2: -lse2, 1 / 3: -delta; the pairs write the same bytes). Rows >= L read as zero: they add
+  // nothing to dV or dK whatever P is.
   const int rs2q = a.rs_q * 2, rs2d = a.rs_do * 2;
-  const rsrc_t rq = make_rsrc(a.q + b * a.bs_q + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2q + DH * 2);
-  const rsrc_t rd = make_rsrc(a.dout + b * a.bs_do + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2d + DH * 2);
+  const rsrc_t rq = hs_rows_rsrc(a.q + b * a.bs_q + hh * a.hs, rs2q, L);
+  const rsrc_t rd = hs_rows_rsrc(a.dout + b * a.bs_do + hh * a.hs, rs2d, L);
   const rsrc_t rr = make_rsrc(a.delta + ((long long)b * a.H + hh) * 2 * L + (wave & 1) * L, (uint32_t)L * 4);
-  // row = 16 wave + 8 j + prow (piece j = 0, 1): g(row) = ((row >> 2) & 3) | ((row >> 1) & 1) << 2 = (2j + (prow >> 2))
-  // | ((prow >> 1) & 1) << 2
-  const int prow = lane >> 3;
-  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
-  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
-  const int dq0 = (16 * wave + prow) * rs2q + 16 * pch0, dq1 = (16 * wave + 8 + prow) * rs2q + 16 * pch1;
-  const int dd0 = (16 * wave + prow) * rs2d + 16 * pch0, dd1 = (16 * wave + 8 + prow) * rs2d + 16 * pch1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
+  const HsRing ring = hs_ring(rq, rs2q, rd, rs2d, lane, wave, smem);
+  const unsigned lds0 = ring.lds0;
   auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-4) of tile t
-    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rq, dq0, t * KT * rs2q, sb + 2048 * wave);
-    if (i == 1) hs_dma16(rq, dq1, t * KT * rs2q, sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rd, dd0, t * KT * rs2d, sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rd, dd1, t * KT * rs2d, sb + TILE_B + 2048 * wave + 1024);
-    if (i == 4) hs_dma4(rr, lane * 4, t * KT * 4, lds0 + (unsigned)(NSLOT * SLOT_B + (t & (NSLOT - 1)) * RC_B +
-                                                                     (wave & 1) * KT * 4));
+    if (i < 4) ring.dma(t, i);
+    if (i == 4) hs_dma4(rr, lane * 4, t * KT * 4,
+                        lds0 + (unsigned)(HS_NSLOT * HS_SLOT_B + (t & (HS_NSLOT - 1)) * RC_B + (wave & 1) * KT * 4));
   };
   auto dma_tile = [&](int t) __attribute__((always_inline)) {
 #pragma unroll
@@ -337,12 +387,12 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
       t_off[db][part] = 2 * sw128(4 * h + ((lane & 15) >> 2) + 8 * part, 32 * db + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
       HS_OPAQUE(t_off[db][part]);
     }
-  rc_off = NSLOT * SLOT_B + 16 * h;   // (past the 64-KB ring: in the register, the rest is an immediate)
+  rc_off = HS_NSLOT * HS_SLOT_B + 16 * h;   // (past the 64-KB ring: in the register, the rest is an immediate)
   HS_OPAQUE(rc_off);
   // DPPRC: lane l reads the constant of query (l & 3) + 8 ((l >> 2) & 3) + 4h, register l & 15's row
-  unsigned rcx_off = NSLOT * SLOT_B + 4 * ((lane & 3) + 8 * ((lane >> 2) & 3) + 4 * h);
+  unsigned rcx_off = HS_NSLOT * HS_SLOT_B + 4 * ((lane & 3) + 8 * ((lane >> 2) & 3) + 4 * h);
   HS_OPAQUE(rcx_off);
-  // soff: byte offset of the tile in the ring (slot, + TILE_B for dO); r0: the half's first query row in the tile
+  // soff: byte offset of the tile in the ring (slot, + HS_TILE_B for dO); r0: the half's first query row in the tile
   auto qrow = [&](int soff, int r0, int ks) __attribute__((always_inline)) {
     return *(const bf16x8*)(smem + q_off[ks] + (soff + 2 * DH * r0));
   };
@@ -432,7 +482,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
   auto tr_load = [&](int f, int st, int soff, int r0) __attribute__((always_inline)) {
     const int s2 = f >> 2, db = (f >> 1) & 1;
     if (f & 1) tq[st][db][s2] = trf(soff, r0, s2, db);
-    else tdo[st][db][s2] = trf(soff + TILE_B, r0, s2, db);
+    else tdo[st][db][s2] = trf(soff + HS_TILE_B, r0, s2, db);
   };
   // one f32x4 piece (queries 8g + 4h .. + 3 of the half) of a chain's row-constant block; rcoff: the tile's
   // row-constant slot, bytes from the end of the ring
@@ -498,7 +548,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
       if (g >= 2 && g < 6) qa[g - 2] = qrow(nslot, nr0, g - 2);
       if (g >= 6) {
         if (!DPPRC) rc_load(NLs[0], nrc, 0, nr0, g - 6);
-        da[g - 6] = qrow(nslot + TILE_B, nr0, g - 6);
+        da[g - 6] = qrow(nslot + HS_TILE_B, nr0, g - 6);
       }
       sgap(2, g);
     }
@@ -510,7 +560,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
       if (DPPRC) bc_gap(11 + g, NST);
       if (g < 2) { if (!DPPRC) rc_load(NLs[0], nrc, 0, nr0, g + 2); }
       else if (g < 6) { if (!DPPRC) rc_load(NDs[0], nrc, 1, nr0, g - 2); }
-      else da[g - 4] = qrow(nslot + TILE_B, nr0, g - 4);
+      else da[g - 4] = qrow(nslot + HS_TILE_B, nr0, g - 4);
       sgap(3, g);
     }
   };
@@ -521,12 +571,10 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
   u32x4 rsq[4];
   uint32_t rsr = 0;
   const unsigned wst = lds0 + 2048 * wave + 16 * lane;
-  const unsigned wrc = lds0 + NSLOT * SLOT_B + (wave & 1) * KT * 4 + 4 * lane;   // (past the ring: in the register)
+  // (past the ring: in the register)
+  const unsigned wrc = lds0 + HS_NSLOT * HS_SLOT_B + (wave & 1) * KT * 4 + 4 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) rsq[0] = hs_ld16(rq, dq0, t * KT * rs2q);
-    if (i == 1) rsq[1] = hs_ld16(rq, dq1, t * KT * rs2q);
-    if (i == 2) rsq[2] = hs_ld16(rd, dd0, t * KT * rs2d);
-    if (i == 3) rsq[3] = hs_ld16(rd, dd1, t * KT * rs2d);
+    if (i < 4) rsq[i] = hs_ld16(ring.rsrc(i), ring.voff(i), ring.soff(t, i));
     if (i == 4) rsr = hs_ld4(rr, lane * 4, t * KT * 4);
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging registers (5 memory operations per wave and tile)
@@ -539,7 +587,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     qa[ks] = qrow(0, 0, ks);
-    da[ks] = qrow(TILE_B, 0, ks);
+    da[ks] = qrow(HS_TILE_B, 0, ks);
   }
   // the prologue's reads complete here (a waitcnt the compiler's pass sees): otherwise its wait for them, merged
   // into the loop header with the back edge's, makes every tile start with lgkmcnt(1)
@@ -548,8 +596,9 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
   // the lane registers above) or, SL < 0, t & 3 at run time
   auto tile = [&](auto SL, int t) __attribute__((always_inline)) {
     constexpr int SLC = decltype(SL)::value;
-    const int sl = SLC >= 0 ? SLC : t & (NSLOT - 1), nsl = SLC >= 0 ? (SLC + 1) & (NSLOT - 1) : (t + 1) & (NSLOT - 1);
-    const int slot = sl * SLOT_B, nslot = nsl * SLOT_B, rc = sl * RC_B, nrc = nsl * RC_B;
+    const int sl = SLC >= 0 ? SLC : t & (HS_NSLOT - 1);
+    const int nsl = SLC >= 0 ? (SLC + 1) & (HS_NSLOT - 1) : (t + 1) & (HS_NSLOT - 1);
+    const int slot = sl * HS_SLOT_B, nslot = nsl * HS_SLOT_B, rc = sl * RC_B, nrc = nsl * RC_B;
     // tile t+1 (stored from registers in half 0) is published after seg A of half 1 (seg C of half 1 is its first
     // reader): one barrier; no LDS fence: the stores were ordered by the waits of this wave's own later reads
     auto stage = [&]() __attribute__((always_inline)) {
@@ -561,16 +610,16 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
       if (!(g & 1)) return;
       constexpr int SS = 0, LS = 2;   // store / load segments of half 0
       if (!(LCI_DKDV_PROBE & 2) && seg == SS && g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
-      constexpr int S1 = SLC >= 0 ? ((SLC + 1) & (NSLOT - 1)) * SLOT_B : 0;
-      constexpr int R1 = SLC >= 0 ? ((SLC + 1) & (NSLOT - 1)) * RC_B : 0;
+      constexpr int S1 = SLC >= 0 ? ((SLC + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : 0;
+      constexpr int R1 = SLC >= 0 ? ((SLC + 1) & (HS_NSLOT - 1)) * RC_B : 0;
       const unsigned base = SLC >= 0 ? wst : wst + (unsigned)nslot;
       const unsigned rbase = SLC >= 0 ? wrc : wrc + (unsigned)nrc;
       if (seg == SS) {
         switch (g) {
           case 1: hs_st16<S1>(base, rsq[0]); break;
           case 3: hs_st16<S1 + 1024>(base, rsq[1]); break;
-          case 5: hs_st16<S1 + TILE_B>(base, rsq[2]); break;
-          default: hs_st16<S1 + TILE_B + 1024>(base, rsq[3]); hs_st4<R1>(rbase, rsr); break;
+          case 5: hs_st16<S1 + HS_TILE_B>(base, rsq[2]); break;
+          default: hs_st16<S1 + HS_TILE_B + 1024>(base, rsq[3]); hs_st4<R1>(rbase, rsr); break;
         }
       }
       if (seg == LS) {
@@ -701,11 +750,7 @@ constexpr unsigned char DQ_SCHED[24][4] = {
 constexpr bool DQ_EARLY = LCI_DQ_EARLY != 0;
 // (the body of attn_bwd_dq_hs_kernel and of attn_bwd_dq_hsfb_kernel, the wide kernel's fallback, below)
 __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
-  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
-  constexpr int SLOT_B = 2 * TILE_B;                // K | V
-  constexpr int NSLOT = 4;
-  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hh = blockIdx.y, b = blockIdx.z;
@@ -727,18 +772,7 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
     for (int qb = 0; qb < 2; ++qb) {
       const int q = qw0 + 32 * qb + r32;
       float nl = 0.f, nd = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if (q < L) {
-          qf[qb][ks] = *(const bf16x8*)(qp + (long long)q * a.rs_q + 16 * ks + 8 * h);
-          df[qb][ks] = *(const bf16x8*)(dop + (long long)q * a.rs_do + 16 * ks + 8 * h);
-        } else {
-          qf[qb][ks] = bf16x8{};
-          df[qb][ks] = bf16x8{};
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[qb][ks][j] = to_bf16(to_f32(qf[qb][ks][j]) * a.c);
-      }
+      hs_load_b2(qf[qb], df[qb], qp, a.rs_q, dop, a.rs_do, q, L, h, a.c);
       if (q < L) { nl = ws[q]; nd = ws[L + q]; }
 #pragma unroll
       for (int i = 0; i < 16; ++i) { NL[qb][i] = nl; ND[qb][i] = nd; }
@@ -753,21 +787,8 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
 
   // ---- K / V tile pieces (wave w: rows 16w .. 16w+15 of each, 1-KB pieces of 8 rows): tile 0 by LDS-DMA
   const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
-  const rsrc_t rk = make_rsrc(a.k + b * a.bs_k + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2k + DH * 2);
-  const rsrc_t rv = make_rsrc(a.v + b * a.bs_v + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2v + DH * 2);
-  const int prow = lane >> 3;
-  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
-  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
-  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
-  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
-  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
-    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rk, dk0, (int)((uint32_t)t * KT * rs2k), sb + 2048 * wave);
-    if (i == 1) hs_dma16(rk, dk1, (int)((uint32_t)t * KT * rs2k), sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rv, dv0, (int)((uint32_t)t * KT * rs2v), sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rv, dv1, (int)((uint32_t)t * KT * rs2v), sb + TILE_B + 2048 * wave + 1024);
-  };
+  const HsRing ring = hs_ring(hs_rows_rsrc(a.k + b * a.bs_k + hh * a.hs, rs2k, L), rs2k,
+                              hs_rows_rsrc(a.v + b * a.bs_v + hh * a.hs, rs2v, L), rs2v, lane, wave, smem);
 
   // LDS byte offsets of every distinct fragment read within a ring slot, computed once and kept opaque (see the
   // forward kernel): with a compile-time ring slot every read is a lane register + an immediate
@@ -786,7 +807,7 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
         HS_OPAQUE(tr_off[r0i][k][part]);
       }
     }
-  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {   // soff: slot (+ TILE_B for V) bytes
+  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {   // soff: slot (+ HS_TILE_B for V) bytes
     return *(const bf16x8*)(smem + row_off[r0i][ks] + soff);
   };
   auto trh = [&](int soff, int r0i, int f, int part) __attribute__((always_inline)) {
@@ -868,10 +889,10 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
       if constexpr (DQ_EARLY) {
         if (g >= 20) {
           kr[g - 20] = row(nsoff, nr0i, g - 20);
-          vr[g - 20] = row(nsoff + TILE_B, nr0i, g - 20);
+          vr[g - 20] = row(nsoff + HS_TILE_B, nr0i, g - 20);
         }
       } else {
-        if (g < 4) vr[g] = row(soff + TILE_B, r0i, g);
+        if (g < 4) vr[g] = row(soff + HS_TILE_B, r0i, g);
         else if (g >= 20) kr[g - 20] = row(nsoff, nr0i, g - 20);
       }
       hook(g);
@@ -881,30 +902,27 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
   // register staging (as the forward's): tile t+1's pieces (loaded into AGPRs during tile
   // t-1) are stored at gaps 1-7 of tile t's half 0, tile t+2's loaded at gaps 9-15; half 1's barrier publishes t+1
   u32x4 stg[4];
-  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  const unsigned wst = ring.lds0 + 2048 * wave + 16 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) stg[0] = hs_ld16(rk, dk0, (int)((uint32_t)t * KT * rs2k));
-    if (i == 1) stg[1] = hs_ld16(rk, dk1, (int)((uint32_t)t * KT * rs2k));
-    if (i == 2) stg[2] = hs_ld16(rv, dv0, (int)((uint32_t)t * KT * rs2v));
-    if (i == 3) stg[3] = hs_ld16(rv, dv1, (int)((uint32_t)t * KT * rs2v));
+    stg[i] = hs_ld16(ring.rsrc(i), ring.voff(i), ring.soff(t, i));
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging registers; wait, publish tile 0; K rows of half 0
-  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ring.dma(0, 0); ring.dma(0, 1); ring.dma(0, 2); ring.dma(0, 3);
   ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
   hs_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     kr[ks] = row(0, 0, ks);
-    if (DQ_EARLY) vr[ks] = row(TILE_B, 0, ks);
+    if (DQ_EARLY) vr[ks] = row(HS_TILE_B, 0, ks);
   }
   __builtin_amdgcn_s_waitcnt(LGKM0_WAIT);   // (see the dK/dV kernel's loop header)
 
   // SL >= 0: tile t sits in ring slot SL (compile-time: DS immediates); SL < 0: slot t & 3 at run time
   auto tile = [&](auto SL, int t) __attribute__((always_inline)) {
     constexpr int sl = decltype(SL)::value;
-    const int soff = sl >= 0 ? sl * SLOT_B : (t & (NSLOT - 1)) * SLOT_B;
-    const int nsoff = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : ((t + 1) & (NSLOT - 1)) * SLOT_B;
+    const int soff = sl >= 0 ? sl * HS_SLOT_B : (t & (HS_NSLOT - 1)) * HS_SLOT_B;
+    const int nsoff = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : ((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B;
     // tile t+1 is published at gap 6 of half 1 (its first reader: the K rows at gaps 20-23)
     auto stage = [&](int g) __attribute__((always_inline)) {
       if (t + 1 < nkt4 && g == 6) __builtin_amdgcn_s_barrier();
@@ -912,13 +930,13 @@ __device__ __forceinline__ void attn_bwd_dq_hs_body(const AttnArgs& a) {
     auto stage0 = [&](int g) __attribute__((always_inline)) {
       if (g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
       if (g < 8 && (g & 1)) {
-        constexpr int S1 = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : 0;
-        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (NSLOT - 1)) * SLOT_B);
+        constexpr int S1 = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : 0;
+        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B);
         switch (g) {
           case 1: hs_st16<S1>(base, stg[0]); break;
           case 3: hs_st16<S1 + 1024>(base, stg[1]); break;
-          case 5: hs_st16<S1 + TILE_B>(base, stg[2]); break;
-          default: hs_st16<S1 + TILE_B + 1024>(base, stg[3]); break;
+          case 5: hs_st16<S1 + HS_TILE_B>(base, stg[2]); break;
+          default: hs_st16<S1 + HS_TILE_B + 1024>(base, stg[3]); break;
         }
       } else if (g >= 9 && g < 16 && (g & 1)) {
         ld_piece(t + 2, (g - 9) >> 1);
@@ -1121,12 +1139,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hsfb_kernel(AttnArg
 __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs a) {
   constexpr int NQB = DQ4_NQB;
   constexpr int NG = DQ4_NG;
-  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
-  constexpr int SLOT_B = 2 * TILE_B;                // K | V
   constexpr int HALF_B = 32 * DH * 2;               // rows 32-63 of a tile: sw128 is invariant under 16-row steps
-  constexpr int NSLOT = 4;
-  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B];
   __shared__ int flagged_wg;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1179,18 +1193,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
       const int q = qw0 + 32 * qb + r32;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        if (q < L) {
-          qf[qb][ks] = *(const bf16x8*)(qp + (long long)q * a.rs_q + 16 * ks + 8 * h);
-          df[qb][ks] = *(const bf16x8*)(dop + (long long)q * a.rs_do + 16 * ks + 8 * h);
-        } else {
-          qf[qb][ks] = bf16x8{};
-          df[qb][ks] = bf16x8{};
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) qf[qb][ks][j] = to_bf16(to_f32(qf[qb][ks][j]) * a.c);
-      }
+      hs_load_b2(qf[qb], df[qb], qp, a.rs_q, dop, a.rs_do, q, L, h, a.c);
       hs_vmcnt<0>();   // (no compiler vmcnt wait inside the loop; per block: the fragments go to AGPRs at once)
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) { HS_TO_AGPR(qf[qb][ks]); HS_TO_AGPR(df[qb][ks]); }
@@ -1199,23 +1202,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
 
   // ---- K / V tile pieces (wave w: rows 16w .. 16w+15 of each, 1-KB pieces of 8 rows): tile 0 by LDS-DMA
   const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
-  const rsrc_t rk = make_rsrc(a.k + b * a.bs_k + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2k + DH * 2);
-  const rsrc_t rv = make_rsrc(a.v + b * a.bs_v + hh * a.hs, (uint32_t)(L - 1) * (uint32_t)rs2v + DH * 2);
-  const int prow = lane >> 3;
-  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
-  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
-  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
-  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
-  // byte offset of tile t's pieces: unsigned, tiles up to nkt4 + 1 are addressed (past L: out of range, zeros)
-  auto toff = [&](int t, int rs2) __attribute__((always_inline)) { return (int)((uint32_t)t * KT * (uint32_t)rs2); };
-  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
-    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rk, dk0, toff(t, rs2k), sb + 2048 * wave);
-    if (i == 1) hs_dma16(rk, dk1, toff(t, rs2k), sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rv, dv0, toff(t, rs2v), sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rv, dv1, toff(t, rs2v), sb + TILE_B + 2048 * wave + 1024);
-  };
+  const HsRing ring = hs_ring(hs_rows_rsrc(a.k + b * a.bs_k + hh * a.hs, rs2k, L), rs2k,
+                              hs_rows_rsrc(a.v + b * a.bs_v + hh * a.hs, rs2v, L), rs2v, lane, wave, smem);
 
   // LDS byte offsets of the fragment reads of rows 0-31 within a ring slot (opaque lane registers, as the narrow
   // kernel's); rows 32-63 and the ring slot are DS immediates
@@ -1232,7 +1220,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
       HS_OPAQUE(tr_off[k][part]);
     }
   }
-  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {   // soff: slot (+ TILE_B for V) bytes
+  auto row = [&](int soff, int r0i, int ks) __attribute__((always_inline)) {   // soff: slot (+ HS_TILE_B for V) bytes
     return *(const bf16x8*)(smem + row_off[ks] + (soff + r0i * HALF_B));
   };
   auto trh = [&](int soff, int r0i, int f, int part) __attribute__((always_inline)) {
@@ -1303,7 +1291,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
       } else if constexpr (g >= KR0 && g < KR0 + 4) {
         kr[g - KR0] = row(nsoff, nr0i, g - KR0);
       } else if constexpr (g >= VR0) {
-        vr[g - VR0] = row(nsoff + TILE_B, nr0i, g - VR0);
+        vr[g - VR0] = row(nsoff + HS_TILE_B, nr0i, g - VR0);
       }
       hook(g);
     }, std::make_integer_sequence<int, NG>{});
@@ -1312,28 +1300,25 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
   // register staging as the narrow kernel's, in arch VGPRs: tile t+1's pieces (loaded during tile t-1) are stored at
   // gaps 1-7 of tile t's half 0, tile t+2's loaded at gaps 9-15; half 1's barrier publishes t+1
   u32x4 stg[4];
-  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  const unsigned wst = ring.lds0 + 2048 * wave + 16 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) stg[0] = hs_ld16v(rk, dk0, toff(t, rs2k));
-    if (i == 1) stg[1] = hs_ld16v(rk, dk1, toff(t, rs2k));
-    if (i == 2) stg[2] = hs_ld16v(rv, dv0, toff(t, rs2v));
-    if (i == 3) stg[3] = hs_ld16v(rv, dv1, toff(t, rs2v));
+    stg[i] = hs_ld16v(ring.rsrc(i), ring.voff(i), ring.soff(t, i));
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging registers; wait, publish tile 0; K / V rows of half 0
-  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ring.dma(0, 0); ring.dma(0, 1); ring.dma(0, 2); ring.dma(0, 3);
   ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
   hs_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     kr[ks] = row(0, 0, ks);
-    vr[ks] = row(TILE_B, 0, ks);
+    vr[ks] = row(HS_TILE_B, 0, ks);
   }
   __builtin_amdgcn_s_waitcnt(LGKM0_WAIT);
 
   auto tile = [&](auto SL, int t) __attribute__((always_inline)) {   // tile t sits in ring slot SL (DS immediates)
     constexpr int sl = decltype(SL)::value;
-    constexpr int soff = sl * SLOT_B, nsoff = ((sl + 1) & (NSLOT - 1)) * SLOT_B;
+    constexpr int soff = sl * HS_SLOT_B, nsoff = ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B;
     // tile t+1 is published at gap 6 of half 1 (its first reader: the K rows at gaps 40-43)
     auto stage = [&](int g) __attribute__((always_inline)) {
       if (t + 1 < nkt4 && g == 6) __builtin_amdgcn_s_barrier();
@@ -1344,8 +1329,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dq_hs4_kernel(AttnArgs
         switch (g) {
           case 1: hs_st16v<nsoff>(wst, stg[0]); break;
           case 3: hs_st16v<nsoff + 1024>(wst, stg[1]); break;
-          case 5: hs_st16v<nsoff + TILE_B>(wst, stg[2]); break;
-          default: hs_st16v<nsoff + TILE_B + 1024>(wst, stg[3]); break;
+          case 5: hs_st16v<nsoff + HS_TILE_B>(wst, stg[2]); break;
+          default: hs_st16v<nsoff + HS_TILE_B + 1024>(wst, stg[3]); break;
         }
       } else if (g >= 9 && g < 16 && (g & 1)) {
         ld_piece(t + 2, (g - 9) >> 1);
@@ -1494,11 +1479,7 @@ __host__ __device__ constexpr bool fw_wrapped_exp(int i) {
 #define LCI_FWD_PROBE 0
 #endif
 __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, const float* knorm) {
-  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
-  constexpr int SLOT_B = 2 * TILE_B;                // K | V
-  constexpr int NSLOT = 4;
-  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B];
   __shared__ int unsafe_wg;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1650,22 +1631,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) HS_TO_AGPR(qf[i][j]);
-  const rsrc_t rk = make_rsrc(kp, (uint32_t)(L - 1) * (uint32_t)(a.rs_k * 2) + DH * 2);
-  const rsrc_t rv = make_rsrc(vp, (uint32_t)(L - 1) * (uint32_t)(a.rs_v * 2) + DH * 2);
   const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
-  const int prow = lane >> 3;
-  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
-  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
-  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
-  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
-  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
-    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rk, dk0, t * KT * rs2k, sb + 2048 * wave);
-    if (i == 1) hs_dma16(rk, dk1, t * KT * rs2k, sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rv, dv0, t * KT * rs2v, sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rv, dv1, t * KT * rs2v, sb + TILE_B + 2048 * wave + 1024);
-  };
+  const HsRing ring = hs_ring(hs_rows_rsrc(kp, rs2k, L), rs2k, hs_rows_rsrc(vp, rs2v, L), rs2v, lane, wave, smem);
   // LDS byte offsets of every distinct fragment read within a ring slot, computed once (the swizzle XOR per row
   // included) and kept opaque: with the slot a compile-time constant (the 4-tile unroll below) each read is then one
   // ds_read with a lane register and an immediate, no address VALU in the loop
@@ -1680,7 +1647,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
       for (int part = 0; part < 2; ++part) {   // fragment k = (d block k & 1, k-step k >> 1)
         const int rw = 32 * r0i + 16 * (k >> 1) + 4 * h + ((lane & 15) >> 2) + 8 * part;
         const int col = 32 * (k & 1) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        tr_off[r0i][k][part] = TILE_B + 2 * sw128(rw, col);
+        tr_off[r0i][k][part] = HS_TILE_B + 2 * sw128(rw, col);
         HS_OPAQUE(tr_off[r0i][k][part]);
       }
     }
@@ -1811,15 +1778,12 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
   // t+1. A piece costs a buffer load + a ds_write_b128 instead of an LDS-DMA issue (~56 cycles each, measured).
   // Pieces past the last tile read as zero (buffer range) into slots nobody reads.
   u32x4 stg[4];
-  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  const unsigned wst = ring.lds0 + 2048 * wave + 16 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) stg[0] = hs_ld16(rk, dk0, t * KT * rs2k);
-    if (i == 1) stg[1] = hs_ld16(rk, dk1, t * KT * rs2k);
-    if (i == 2) stg[2] = hs_ld16(rv, dv0, t * KT * rs2v);
-    if (i == 3) stg[3] = hs_ld16(rv, dv1, t * KT * rs2v);
+    stg[i] = hs_ld16(ring.rsrc(i), ring.voff(i), ring.soff(t, i));
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging AGPRs; wait for tile 0; K rows of its first half
-  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ring.dma(0, 0); ring.dma(0, 1); ring.dma(0, 2); ring.dma(0, 3);
   ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
   hs_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
@@ -1831,8 +1795,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
   auto tile = [&](auto SL, int t, const f32x16& a0, const f32x16& a1, const f32x16& b0, const f32x16& b1)
       __attribute__((always_inline)) {
     constexpr int sl = decltype(SL)::value;
-    const int soff = sl >= 0 ? sl * SLOT_B : (t & (NSLOT - 1)) * SLOT_B;
-    const int nsoff = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : ((t + 1) & (NSLOT - 1)) * SLOT_B;
+    const int soff = sl >= 0 ? sl * HS_SLOT_B : (t & (HS_NSLOT - 1)) * HS_SLOT_B;
+    const int nsoff = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : ((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B;
     // tile t+1 is published at gap 6 of half 1 (first reader: the K rows at gaps 12-15)
     auto stage = [&](int g) __attribute__((always_inline)) {
       if (!(LCI_FWD_PROBE & 1) && t + 1 < nkt && g == 7) __builtin_amdgcn_s_barrier();
@@ -1841,13 +1805,13 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs_kernel(AttnArgs a, 
     auto rstg = [&](int g) __attribute__((always_inline)) {
       if (!(LCI_FWD_PROBE & 2) && g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
       if (g < 8 && (g & 1)) {
-        constexpr int S1 = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : 0;
-        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (NSLOT - 1)) * SLOT_B);
+        constexpr int S1 = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : 0;
+        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B);
         switch (g) {
           case 1: hs_st16<S1>(base, stg[0]); break;
           case 3: hs_st16<S1 + 1024>(base, stg[1]); break;
-          case 5: hs_st16<S1 + TILE_B>(base, stg[2]); break;
-          default: hs_st16<S1 + TILE_B + 1024>(base, stg[3]); break;
+          case 5: hs_st16<S1 + HS_TILE_B>(base, stg[2]); break;
+          default: hs_st16<S1 + HS_TILE_B + 1024>(base, stg[3]); break;
         }
       } else if (g >= LD0 && g < LD0 + 8 && ((g - LD0) & 1) == 0) {
         ld_piece(t + 2, (g - LD0) >> 1);
@@ -2037,11 +2001,7 @@ __host__ __device__ constexpr bool fw4_add_wraps(int qb) { return 10 * qb + 22 >
 
 __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a, const float* knorm) {
   constexpr int NQB = FW4_NQB;
-  constexpr int TILE_B = KT * DH * 2;               // bytes of a K or V tile (128-B rows)
-  constexpr int SLOT_B = 2 * TILE_B;                // K | V
-  constexpr int NSLOT = 4;
-  static_assert(NSLOT * SLOT_B == 65536, "ring reachable by DS immediates");
-  __shared__ __attribute__((aligned(16))) char smem[NSLOT * SLOT_B];
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B];
   __shared__ int unsafe_wg;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2219,22 +2179,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a,
   for (int i = 0; i < NQB; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) HS_TO_AGPR(qf[i][j]);
-  const rsrc_t rk = make_rsrc(kp, (uint32_t)(L - 1) * (uint32_t)(a.rs_k * 2) + DH * 2);
-  const rsrc_t rv = make_rsrc(vp, (uint32_t)(L - 1) * (uint32_t)(a.rs_v * 2) + DH * 2);
   const int rs2k = a.rs_k * 2, rs2v = a.rs_v * 2;
-  const int prow = lane >> 3;
-  const int pch0 = (lane & 7) ^ ((prow >> 2) | ((prow >> 1) & 1) << 2);
-  const int pch1 = (lane & 7) ^ ((2 + (prow >> 2)) | ((prow >> 1) & 1) << 2);
-  const int dk0 = (16 * wave + prow) * rs2k + 16 * pch0, dk1 = (16 * wave + 8 + prow) * rs2k + 16 * pch1;
-  const int dv0 = (16 * wave + prow) * rs2v + 16 * pch0, dv1 = (16 * wave + 8 + prow) * rs2v + 16 * pch1;
-  const unsigned lds0 = (unsigned)(uintptr_t)(LCI_LDS char*)smem;
-  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-3) of tile t
-    const unsigned sb = lds0 + (unsigned)((t & (NSLOT - 1)) * SLOT_B);
-    if (i == 0) hs_dma16(rk, dk0, t * KT * rs2k, sb + 2048 * wave);
-    if (i == 1) hs_dma16(rk, dk1, t * KT * rs2k, sb + 2048 * wave + 1024);
-    if (i == 2) hs_dma16(rv, dv0, t * KT * rs2v, sb + TILE_B + 2048 * wave);
-    if (i == 3) hs_dma16(rv, dv1, t * KT * rs2v, sb + TILE_B + 2048 * wave + 1024);
-  };
+  const HsRing ring = hs_ring(hs_rows_rsrc(kp, rs2k, L), rs2k, hs_rows_rsrc(vp, rs2v, L), rs2v, lane, wave, smem);
   // LDS byte offsets of every distinct fragment read within a ring slot (as attn_fwd_hs_kernel)
   unsigned row_off[2][4], tr_off[2][4][2];   // [rows 0-31 | 32-63][k-step | fragment][part]
 #pragma unroll
@@ -2247,7 +2193,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a,
       for (int part = 0; part < 2; ++part) {   // fragment k = (d block k & 1, k-step k >> 1)
         const int rw = 32 * r0i + 16 * (k >> 1) + 4 * h + ((lane & 15) >> 2) + 8 * part;
         const int col = 32 * (k & 1) + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-        tr_off[r0i][k][part] = TILE_B + 2 * sw128(rw, col);
+        tr_off[r0i][k][part] = HS_TILE_B + 2 * sw128(rw, col);
         HS_OPAQUE(tr_off[r0i][k][part]);
       }
     }
@@ -2380,15 +2326,12 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a,
   // t's half 0 and tile t+2's loaded at gaps 11-17; the barrier at gap 7 of tile t's half 1 publishes tile t+1 (first
   // reader: the K rows at gaps KR0 ..)
   u32x4 stg[4];
-  const unsigned wst = lds0 + 2048 * wave + 16 * lane;
+  const unsigned wst = ring.lds0 + 2048 * wave + 16 * lane;
   auto ld_piece = [&](int t, int i) __attribute__((always_inline)) {
-    if (i == 0) stg[0] = hs_ld16(rk, dk0, t * KT * rs2k);
-    if (i == 1) stg[1] = hs_ld16(rk, dk1, t * KT * rs2k);
-    if (i == 2) stg[2] = hs_ld16(rv, dv0, t * KT * rs2v);
-    if (i == 3) stg[3] = hs_ld16(rv, dv1, t * KT * rs2v);
+    stg[i] = hs_ld16(ring.rsrc(i), ring.voff(i), ring.soff(t, i));
   };
   // prologue: tile 0 by LDS-DMA, tile 1 into the staging AGPRs; wait for tile 0; K rows of its first half
-  dma_op(0, 0); dma_op(0, 1); dma_op(0, 2); dma_op(0, 3);
+  ring.dma(0, 0); ring.dma(0, 1); ring.dma(0, 2); ring.dma(0, 3);
   ld_piece(1, 0); ld_piece(1, 1); ld_piece(1, 2); ld_piece(1, 3);
   hs_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
@@ -2401,8 +2344,8 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a,
   auto tile = [&](auto SL, int t, const f32x16 (&ia)[NQB], const f32x16 (&ib)[NQB], auto mid)
       __attribute__((always_inline)) {
     constexpr int sl = decltype(SL)::value;
-    const int soff = sl >= 0 ? sl * SLOT_B : (t & (NSLOT - 1)) * SLOT_B;
-    const int nsoff = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : ((t + 1) & (NSLOT - 1)) * SLOT_B;
+    const int soff = sl >= 0 ? sl * HS_SLOT_B : (t & (HS_NSLOT - 1)) * HS_SLOT_B;
+    const int nsoff = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : ((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B;
     auto stage = [&](int g) __attribute__((always_inline)) {
       if (t + 1 < nkt && g == 7) __builtin_amdgcn_s_barrier();
     };
@@ -2410,13 +2353,13 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_fwd_hs4_kernel(AttnArgs a,
     auto rstg = [&](int g) __attribute__((always_inline)) {
       if (g == 1) hs_vmcnt<0>();   // tile t+1's pieces (loaded a tile ago)
       if (g < 8 && (g & 1)) {
-        constexpr int S1 = sl >= 0 ? ((sl + 1) & (NSLOT - 1)) * SLOT_B : 0;
-        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (NSLOT - 1)) * SLOT_B);
+        constexpr int S1 = sl >= 0 ? ((sl + 1) & (HS_NSLOT - 1)) * HS_SLOT_B : 0;
+        const unsigned base = sl >= 0 ? wst : wst + (unsigned)(((t + 1) & (HS_NSLOT - 1)) * HS_SLOT_B);
         switch (g) {
           case 1: hs_st16<S1>(base, stg[0]); break;
           case 3: hs_st16<S1 + 1024>(base, stg[1]); break;
-          case 5: hs_st16<S1 + TILE_B>(base, stg[2]); break;
-          default: hs_st16<S1 + TILE_B + 1024>(base, stg[3]); break;
+          case 5: hs_st16<S1 + HS_TILE_B>(base, stg[2]); break;
+          default: hs_st16<S1 + HS_TILE_B + 1024>(base, stg[3]); break;
         }
       } else if (g >= LD0 && g < LD0 + 8 && ((g - LD0) & 1) == 0) {
         ld_piece(t + 2, (g - LD0) >> 1);
@@ -2513,6 +2456,34 @@ static int check_packed(const void* p, int rs) {
   return ((uintptr_t)p % 16 == 0) && (rs % 8 == 0);
 }
 
+// The checks lci_attn_fwd* and lci_attn_bwd* share (`what` names the entry point in the messages): head dim, shape,
+// alignment of the packed qkv-layout tensors (qkv; dqkv in the backward) and of the (B, L, H*64) ones (out; dout), and
+// the 32-bit range of the placed kernels' buffer offsets. They address rows through buffer resources with 32-bit
+// sizes and stage key tiles up to two past the tile count padded to a multiple of 4: rows below L + 6 KT.
+static int attn_check(const char* what, const void* qkv, const void* dqkv, const void* out, const void* dout, int B,
+                      int L, int H, int head_dim) {
+  LCI_CHECK(head_dim == DH, "%s: head_dim %d unsupported (only 64)", what, head_dim);
+  LCI_CHECK(B > 0 && L > 0 && H > 0, "%s: bad shape B=%d L=%d H=%d", what, B, L, H);
+  const int rs = 3 * H * DH;
+  LCI_CHECK(check_packed(qkv, rs) && (!dqkv || check_packed(dqkv, rs)) && check_packed(out, H * DH) &&
+                (!dout || check_packed(dout, H * DH)), "%s: misaligned pointers", what);
+  LCI_CHECK((long long)(L + 6 * KT) * rs * 2 < (1ll << 31), "%s: L=%d too long for 32-bit buffer offsets", what, L);
+  return 0;
+}
+
+// The AttnArgs fields forward and backward share: q | k | v inside the packed qkv (B, L, 3*H*64), shape and scales
+static AttnArgs attn_args(const void* qkv, int L, int H, float scale) {
+  AttnArgs a{};
+  const int rs = 3 * H * DH;
+  const bf16* base = (const bf16*)qkv;
+  a.q = base; a.k = base + H * DH; a.v = base + 2 * H * DH;
+  a.bs_q = a.bs_k = a.bs_v = (long long)L * rs;
+  a.rs_q = a.rs_k = a.rs_v = rs;
+  a.hs = DH; a.H = H; a.L = L;
+  a.scale = scale; a.c = scale * 1.4426950408889634f;
+  return a;
+}
+
 extern "C" long long lci_attn_fwd_ws_bytes(int B, int L, int H) {
   return (long long)B * H * ((L + KT - 1) / KT) * sizeof(float);
 }
@@ -2546,22 +2517,11 @@ static int attn_n_cu() {   // compute units of the current device, asked once pe
 extern "C" int lci_attn_fwd_variant(int variant, const void* qkv, void* out, float* lse2, float* knorm_ws, int B,
                                     int L, int H, int head_dim, float scale, void* stream) {
   LCI_CHECK(variant >= -1 && variant <= 1, "lci_attn_fwd_variant: variant %d (want -1, 0 or 1)", variant);
-  LCI_CHECK(head_dim == DH, "lci_attn_fwd: head_dim %d unsupported (only 64)", head_dim);
-  LCI_CHECK(B > 0 && L > 0 && H > 0, "lci_attn_fwd: bad shape B=%d L=%d H=%d", B, L, H);
-  const int rs = 3 * H * DH;
-  LCI_CHECK(check_packed(qkv, rs) && check_packed(out, H * DH), "lci_attn_fwd: misaligned pointers");
-  // the placed kernels stage key tiles up to two past the tile count padded to a multiple of 4: rows below L + 6 KT
-  LCI_CHECK((long long)(L + 6 * KT) * rs * 2 < (1ll << 31), "lci_attn_fwd: L=%d too long for 32-bit buffer offsets", L);
+  if (attn_check("lci_attn_fwd", qkv, nullptr, out, nullptr, B, L, H, head_dim)) return 1;
   LCI_CHECK(knorm_ws != nullptr, "lci_attn_fwd: knorm_ws (lci_attn_fwd_ws_bytes) is required");
-  AttnArgs a{};
-  const bf16* base = (const bf16*)qkv;
-  a.q = base; a.k = base + H * DH; a.v = base + 2 * H * DH;
+  AttnArgs a = attn_args(qkv, L, H, scale);
   a.out = (bf16*)out; a.lse2 = lse2;
-  a.bs_q = a.bs_k = a.bs_v = (long long)L * rs;
-  a.rs_q = a.rs_k = a.rs_v = rs;
   a.bs_out = (long long)L * H * DH; a.rs_out = H * DH;
-  a.hs = DH; a.H = H; a.L = L;
-  a.scale = scale; a.c = scale * 1.4426950408889634f;
   hipStream_t s = (hipStream_t)stream;
   const int nkt = (L + KT - 1) / KT;
   hipLaunchKernelGGL(attn_key_norm_kernel, dim3((nkt + 3) / 4, H, B), dim3(256), 0, s, a, knorm_ws, nkt);
@@ -2595,30 +2555,17 @@ extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, 
                                     const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H, int head_dim,
                                     float scale, void* stream) {
   LCI_CHECK(dq_variant >= -1 && dq_variant <= 1, "lci_attn_bwd_variant: dq_variant %d (want -1, 0 or 1)", dq_variant);
-  LCI_CHECK(head_dim == DH, "lci_attn_bwd: head_dim %d unsupported (only 64)", head_dim);
-  LCI_CHECK(B > 0 && L > 0 && H > 0, "lci_attn_bwd: bad shape B=%d L=%d H=%d", B, L, H);
-  const int rs = 3 * H * DH;
-  LCI_CHECK(check_packed(qkv, rs) && check_packed(dqkv, rs) && check_packed(out, H * DH) &&
-                check_packed(dout, H * DH), "lci_attn_bwd: misaligned pointers");
-  // the placed kernels address q / k / v / dO rows through buffer resources with 32-bit sizes; the dQ kernels stage
-  // key tiles up to two past the tile count padded to a multiple of 4: rows below L + 6 KT
-  LCI_CHECK((long long)(L + 6 * KT) * rs * 2 < (1ll << 31), "lci_attn_bwd: L=%d too long for 32-bit buffer offsets", L);
+  if (attn_check("lci_attn_bwd", qkv, dqkv, out, dout, B, L, H, head_dim)) return 1;
   LCI_CHECK(delta_ws != nullptr, "lci_attn_bwd: delta_ws (lci_attn_bwd_ws_bytes) is required");
-  AttnArgs a{};
-  const bf16* base = (const bf16*)qkv;
+  AttnArgs a = attn_args(qkv, L, H, scale);
   bf16* dbase = (bf16*)dqkv;
-  a.q = base; a.k = base + H * DH; a.v = base + 2 * H * DH;
   a.o = (const bf16*)out; a.dout = (const bf16*)dout;
   a.lse2 = (float*)lse2; a.delta = delta_ws;
-  a.bs_q = a.bs_k = a.bs_v = (long long)L * rs;
-  a.rs_q = a.rs_k = a.rs_v = rs;
   a.bs_o = a.bs_do = (long long)L * H * DH;
   a.rs_o = a.rs_do = H * DH;
   a.out = dbase; a.dk = dbase + H * DH; a.dv = dbase + 2 * H * DH;
-  a.bs_out = a.bs_dk = a.bs_dv = (long long)L * rs;
-  a.rs_out = a.rs_dk = a.rs_dv = rs;
-  a.hs = DH; a.H = H; a.L = L;
-  a.scale = scale; a.c = scale * 1.4426950408889634f;
+  a.bs_out = a.bs_dk = a.bs_dv = a.bs_q;
+  a.rs_out = a.rs_dk = a.rs_dv = a.rs_q;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((L + HS_NW * 64 - 1) / (HS_NW * 64), H, B);
   if (stage < 0 || stage == 0) {

@@ -53,17 +53,22 @@ class KernelTimer:
 
 
 # ------------------------------------------------------------------------------------- attention
-def attn_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
-    """qkv (B, L, 3*H*64) bf16 -> out (B, L, H*64) bf16, lse2 (B, H, L) f32."""
+def _attn_fwd_setup(qkv: torch.Tensor, num_heads: int, what: str):
+    """Shapes, dtype check, outputs and key-norm workspace of a forward call: (B, L, dh, out, lse2, ws)."""
     _lib.require_gpu(qkv)
     B, L, C = qkv.shape
     dh = C // (3 * num_heads)
     if qkv.dtype != torch.bfloat16:
-        raise _lib.LciError("attn_fwd expects bf16 qkv")
+        raise _lib.LciError(f"{what} expects bf16 qkv")
     out = torch.empty(B, L, num_heads * dh, device=qkv.device, dtype=torch.bfloat16)
     lse2 = torch.empty(B, num_heads, L, device=qkv.device, dtype=torch.float32)
-    ws = torch.empty(_lib.load().lci_attn_fwd_ws_bytes(B, L, num_heads) // 4, device=qkv.device,
-                     dtype=torch.float32)
+    ws = torch.empty(_lib.load().lci_attn_fwd_ws_bytes(B, L, num_heads) // 4, device=qkv.device, dtype=torch.float32)
+    return B, L, dh, out, lse2, ws
+
+
+def attn_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
+    """qkv (B, L, 3*H*64) bf16 -> out (B, L, H*64) bf16, lse2 (B, H, L) f32."""
+    B, L, dh, out, lse2, ws = _attn_fwd_setup(qkv, num_heads, "attn_fwd")
     KernelTimer.run("attn_fwd", 4.0 * B * num_heads * L * L * dh, qkv, lambda: _lib.call(
         "lci_attn_fwd", qkv.data_ptr(), out.data_ptr(), lse2.data_ptr(), ws.data_ptr(), B, L, num_heads, dh,
         float(scale), _lib.stream_of(qkv)))
@@ -73,29 +78,30 @@ def attn_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
 def attn_fwd_variant(qkv: torch.Tensor, num_heads: int, scale: float, variant: int):
     """attn_fwd with the forward kernel forced (include/lci.h lci_attn_fwd_variant: 0 = 64 queries per wave, 1 = 128,
     -1 = the library's pick); for tests and A/B timing."""
-    _lib.require_gpu(qkv)
-    B, L, C = qkv.shape
-    dh = C // (3 * num_heads)
-    if qkv.dtype != torch.bfloat16:
-        raise _lib.LciError("attn_fwd_variant expects bf16 qkv")
-    out = torch.empty(B, L, num_heads * dh, device=qkv.device, dtype=torch.bfloat16)
-    lse2 = torch.empty(B, num_heads, L, device=qkv.device, dtype=torch.float32)
-    ws = torch.empty(_lib.load().lci_attn_fwd_ws_bytes(B, L, num_heads) // 4, device=qkv.device,
-                     dtype=torch.float32)
+    B, L, dh, out, lse2, ws = _attn_fwd_setup(qkv, num_heads, "attn_fwd_variant")
     _lib.call("lci_attn_fwd_variant", int(variant), qkv.data_ptr(), out.data_ptr(), lse2.data_ptr(), ws.data_ptr(), B,
               L, num_heads, dh, float(scale), _lib.stream_of(qkv))
     return out, lse2
 
 
-def attn_bwd(qkv, out, dout, lse2, num_heads: int, scale: float):
+def _attn_bwd_setup(qkv, out, dout, lse2, num_heads: int, scale: float, dqkv=None, ws=None):
+    """Shapes, output, workspace (include/lci.h lci_attn_bwd_ws_bytes, as int32) and the argument list the lci_attn_bwd*
+    entry points share: (B, L, dh, dqkv, ws, args)."""
     _lib.require_gpu(qkv, out, dout, lse2)
     B, L, C = qkv.shape
     dh = C // (3 * num_heads)
-    dqkv = torch.empty_like(qkv)
-    # -lse2 | -delta rows (include/lci.h lci_attn_bwd_ws_bytes)
-    delta = torch.empty(int(_lib.load().lci_attn_bwd_ws_bytes(B, num_heads, L)), device=qkv.device, dtype=torch.uint8)
-    args = (qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse2.data_ptr(), dqkv.data_ptr(), delta.data_ptr(),
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    if ws is None:
+        ws = torch.empty(int(_lib.load().lci_attn_bwd_ws_bytes(B, num_heads, L)) // 4, device=qkv.device,
+                         dtype=torch.int32)
+    args = (qkv.data_ptr(), out.data_ptr(), dout.data_ptr(), lse2.data_ptr(), dqkv.data_ptr(), ws.data_ptr(),
             B, L, num_heads, dh, float(scale), _lib.stream_of(qkv))
+    return B, L, dh, dqkv, ws, args
+
+
+def attn_bwd(qkv, out, dout, lse2, num_heads: int, scale: float):
+    B, L, dh, dqkv, _, args = _attn_bwd_setup(qkv, out, dout, lse2, num_heads, scale)
     if not KernelTimer.enabled:
         _lib.call("lci_attn_bwd", *args)
         return dqkv
@@ -114,16 +120,8 @@ def attn_bwd_variant(qkv, out, dout, lse2, num_heads: int, scale: float, dq_vari
     view of the workspace's per-workgroup flags, written only when the 128-query kernel ran. A single stage (0 = delta,
     1 = dK/dV, 2 = dQ) needs the workspace `ws` of an earlier stage-0 call (an int32 tensor of
     lci_attn_bwd_ws_bytes / 4 elements) and, to keep the other stages' results, its `dqkv`."""
-    _lib.require_gpu(qkv, out, dout, lse2)
-    B, L, C = qkv.shape
-    dh = C // (3 * num_heads)
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    if ws is None:
-        ws = torch.empty(int(_lib.load().lci_attn_bwd_ws_bytes(B, num_heads, L)) // 4, device=qkv.device,
-                         dtype=torch.int32)
-    _lib.call("lci_attn_bwd_variant", int(dq_variant), int(stage), qkv.data_ptr(), out.data_ptr(), dout.data_ptr(),
-              lse2.data_ptr(), dqkv.data_ptr(), ws.data_ptr(), B, L, num_heads, dh, float(scale), _lib.stream_of(qkv))
+    B, L, _, dqkv, ws, args = _attn_bwd_setup(qkv, out, dout, lse2, num_heads, scale, dqkv, ws)
+    _lib.call("lci_attn_bwd_variant", int(dq_variant), int(stage), *args)
     n0, nwg = B * num_heads * 2 * L, (L + 511) // 512
     return dqkv, ws[n0:n0 + B * num_heads * nwg].view(B, num_heads, nwg)
 
