@@ -10,9 +10,9 @@
 // place (B and C are strided column slices of the x_proj output). One wave = 64 channels (lane = channel,
 // 8 fp32 states in registers); B_t / C_t are wave-uniform loads. L is split into chunks of Tc steps:
 //   fwd pass 1 (per chunk, zero init): end state + sum(dt')      fwd pass 2 (per channel/state): carry over chunks
-//   fwd pass 3 (per chunk from the true initial state): y, and x checkpoints every 16 steps for the backward
+//   fwd pass 3 (per chunk from the true initial state): y, and x checkpoints every CKPT = 8 steps for the backward
 //   bwd pass A (per chunk): local adjoint aggregate              bwd pass B: reverse carry over chunks
-//   bwd pass C (per chunk, reverse 16-step sub-blocks recomputed from the checkpoints in registers):
+//   bwd pass C (per chunk, reverse CKPT-step sub-blocks recomputed from the checkpoints in registers):
 //       du, d(dt), dA, dD, d(delta_bias), and per-token dB/dC reduced over channels (butterfly + LDS).
 #include "common.hpp"
 

@@ -50,7 +50,9 @@ def test_selective_scan_vs_reference_fixture():
 
 @pytest.mark.parametrize("L,d,dtype,tol", [(5000, 96, torch.float32, 2e-4), (3001, 64, torch.bfloat16, 3e-2)])
 def test_selective_scan_chunked_long(L, d, dtype, tol):
-    """Many chunks (chunk 256): the cross-chunk carries (fwd and bwd) are exercised; ragged tail."""
+    """Many chunks (chunk 64: 79 / 47 of them): the cross-chunk carries (fwd and bwd) are exercised; ragged tail."""
+    from long_context_biomedical_imaging_amd import kernels
+    assert kernels._scan_chunk(L, 1, d) == 64
     torch.manual_seed(3)
     b, n = 1, 8
     u = torch.randn(b, d, L)
@@ -214,3 +216,73 @@ def test_selective_scan_one_chunk_path_bitwise(nseq, L, d, dtype):
             assert err <= 1e-4 * b.float().abs().max().item() + 1e-6, (name, err)
         else:
             assert torch.equal(a, b), name
+
+
+def _scan_inputs(L, d, dtype, seed):
+    """The project's scan input distributions, rounded to the I/O dtype (the reference sees the same values)."""
+    g = torch.Generator().manual_seed(seed)
+    q = lambda t: t.to(dtype).float()  # noqa: E731
+    u, delta = q(torch.randn(1, d, L, generator=g)), q(torch.randn(1, d, L, generator=g) * 0.5 - 1.0)
+    A = -torch.exp(torch.randn(d, 8, generator=g) * 0.3)
+    Bm, Cm = q(torch.randn(1, 8, L, generator=g)), q(torch.randn(1, 8, L, generator=g))
+    D, db = torch.randn(d, generator=g), torch.randn(d, generator=g) * 0.1
+    return u, delta, A, Bm, Cm, D, db
+
+
+# LCI_SCAN_WAVES is read per call: it steers kernels._scan_chunk to (L, chunk) = (600, 72) and (1550, 520) at Dx 96
+_STEERED = {72: (600, "18"), 520: (1550, "6")}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("tc", [72, 520])
+def test_selective_scan_last_state_steered_chunk(tc, dtype, monkeypatch):
+    """return_last_state = exp(A sdt[-1]) xinit[-1] + xend[-1] against the fp64 final state, at a chunk with a short
+    last staging block (72: 9 chunks) and in the chunk >= 512 regime (520: 3 chunks); the last state is f32 in both
+    dtypes."""
+    from long_context_biomedical_imaging_amd import kernels
+    L, waves = _STEERED[tc]
+    d = 96
+    monkeypatch.setenv("LCI_SCAN_WAVES", waves)
+    assert kernels._scan_chunk(L, 1, d) == tc
+    u, delta, A, Bm, Cm, D, db = _scan_inputs(L, d, dtype, 100 + tc)
+    x_dbl = torch.cat([_cl(Bm), _cl(Cm)], dim=-1).to("cuda", dtype)
+    yz = torch.zeros(1, L, 2 * d, device="cuda", dtype=dtype)
+    out, last = kernels.selective_scan_cl(_cl(u).to("cuda", dtype), _cl(delta).to("cuda", dtype), A.cuda(),
+                                          x_dbl[..., :8], x_dbl[..., 8:], D.cuda(), db.cuda(), yz,
+                                          return_last_state=True)
+    dt = F.softplus(delta.double() + db.double()[:, None])
+    x = torch.zeros(1, d, 8, dtype=torch.float64)
+    for t in range(L):
+        x = torch.exp(dt[:, :, t, None] * A.double()[None]) * x \
+            + (dt[:, :, t] * u.double()[:, :, t])[..., None] * Bm.double()[:, None, :, t]
+    assert last.dtype == torch.float32 and rel_err(last, x) < 1e-4
+    yr = oscan.selective_scan(u.double(), delta.double(), A.double(), Bm.double(), Cm.double(), D.double(),
+                              delta_bias=db.double(), delta_softplus=True)
+    assert rel_err(out[..., :d].transpose(1, 2), yr) < (1e-4 if dtype == torch.float32 else 5e-3)
+
+
+def test_selective_scan_joint_bc_long_chunk_f32(monkeypatch):
+    """The joint [B | C] tensor path (Cm=None: one gradient for both) through autograd in the chunk >= 512 regime (one
+    wave per workgroup, parameter-gradient atomics) in f32, against oracle.selective_scan in fp64."""
+    from long_context_biomedical_imaging_amd import kernels
+    L, waves = _STEERED[520]
+    d = 96
+    monkeypatch.setenv("LCI_SCAN_WAVES", waves)
+    assert kernels._scan_chunk(L, 1, d) == 520
+    u, delta, A, Bm, Cm, D, db = _scan_inputs(L, d, torch.float32, 77)
+    cot = torch.randn(1, d, L, generator=torch.Generator().manual_seed(78))
+    x_dbl = torch.cat([_cl(Bm), _cl(Cm)], dim=-1)
+    leaves = [t.cuda().requires_grad_(True) for t in (_cl(u), _cl(delta), A, x_dbl, D, db)]
+    uc, dc, Ac, bc, Dc, dbc = leaves
+    yz = torch.zeros(1, L, 2 * d, device="cuda")
+    out = kernels.selective_scan_cl(uc, dc, Ac, bc, None, Dc, dbc, yz)
+    (out[..., :d] * _cl(cot).cuda()).sum().backward()
+    ins = [t.double().requires_grad_(True) for t in (u, delta, A, Bm, Cm, D, db)]
+    yr = oscan.selective_scan(*ins[:6], delta_bias=ins[6], delta_softplus=True)
+    (yr * cot.double()).sum().backward()
+    assert rel_err(out[..., :d].transpose(1, 2), yr) < 1e-4
+    got = {"u": uc.grad.transpose(1, 2), "delta": dc.grad.transpose(1, 2), "A": Ac.grad,
+           "B": bc.grad[..., :8].transpose(1, 2), "C": bc.grad[..., 8:].transpose(1, 2), "D": Dc.grad,
+           "delta_bias": dbc.grad}
+    for name, r in zip(["u", "delta", "A", "B", "C", "D", "delta_bias"], ins):
+        assert rel_err(got[name], r.grad) < 2e-4, (name, rel_err(got[name], r.grad))
