@@ -18,9 +18,6 @@
 
 namespace lci {
 
-#ifndef LCI_SCAN_PROBE
-#define LCI_SCAN_PROBE 0   // 1: the transcendental-floor timing probe of the forward passes (build_variant only)
-#endif
 constexpr int SCAN_N = 8;     // d_state (the reference always uses 8: backbone_vit.py:184, backbone_swin.py:329)
 constexpr int CKPT = 8;       // backward checkpoint spacing (steps); sub-block states live in registers
 constexpr float LOG2E = 1.4426950408889634f;
@@ -80,6 +77,8 @@ struct Col {
   }
 };
 
+// The 8 states of one channel (xend, xinit, gl, gin, the partials: f32; checkpoints: the I/O dtype) or one staged
+// B_t / C_t row in LDS, as 16-byte accesses: one for bf16, two for f32.
 template <typename T>
 __device__ __forceinline__ void ld8(const T* p, float (&v)[SCAN_N]) {
   if constexpr (sizeof(T) == 2) {
@@ -93,12 +92,18 @@ __device__ __forceinline__ void ld8(const T* p, float (&v)[SCAN_N]) {
   }
 }
 
-// B/C rows are 16-byte aligned only when the token stride keeps them so; fall back to scalar loads.
-template <typename T>
-__device__ __forceinline__ void ld8u(const T* p, float (&v)[SCAN_N], bool aligned) {
-  if (aligned) { ld8(p, v); return; }
+// v: a float[8], or a Row8 (a raw B_t / C_t row, converted here)
+template <typename T, typename V8>
+__device__ __forceinline__ void st8(T* p, const V8& v) {
+  if constexpr (sizeof(T) == 2) {
+    bf16x8 r;
 #pragma unroll
-  for (int n = 0; n < SCAN_N; ++n) v[n] = (float)p[n];
+    for (int n = 0; n < SCAN_N; ++n) r[n] = to_bf16(v[n]);
+    *(bf16x8*)p = r;
+  } else {
+    *(f32x4*)p = f32x4{v[0], v[1], v[2], v[3]};
+    *(f32x4*)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
+  }
 }
 
 // raw B_t / C_t row (8 values): one 16-B load for bf16, two for f32; converted at use
@@ -138,74 +143,62 @@ __device__ __forceinline__ void decay8(float dt, const float (&A2)[SCAN_N], floa
   }
 }
 
+// B_t / C_t are wave-uniform per step, so a block of SB rows is converted to f32 once and staged in LDS instead of
+// in every lane at every step: lane i loads the Row8s of step tb + i and st8 writes them to LDS row i.
 constexpr int SB = 64;        // steps per LDS-staged block of B_t / C_t rows (one row per lane)
 constexpr int BCS = 20;       // LDS floats per staged row (B 0..7, C 8..15, pad: 80-B rows)
 
-// Stage the f32 B_t (and C_t) rows of steps tb .. tb+SB-1 into this wave's LDS block, lane i <- step tb+i:
-// B/C are wave-uniform per step, so they are converted once here instead of in every lane at every step.
-template <typename T, bool WITH_C>
-__device__ __forceinline__ void stage_bc(const ScanArgs& a, float* bc, const T* Bp, const T* Cp, int tb, int t1,
-                                         int lane) {
-  const long long t = min(tb + lane, t1 - 1);
-  Row8<T> rb;
-  rb.load(Bp + t * a.tB);
-  float* dst = bc + lane * BCS;
-  *(f32x4*)dst = f32x4{rb[0], rb[1], rb[2], rb[3]};
-  *(f32x4*)(dst + 4) = f32x4{rb[4], rb[5], rb[6], rb[7]};
-  if constexpr (WITH_C) {
-    Row8<T> rc;
-    rc.load(Cp + t * a.tC);
-    *(f32x4*)(dst + 8) = f32x4{rc[0], rc[1], rc[2], rc[3]};
-    *(f32x4*)(dst + 12) = f32x4{rc[4], rc[5], rc[6], rc[7]};
+// Per-wave setup shared by the three chunk kernels. The forward and aggregate kernels run one chunk per wave
+// (CPW = 4 chunks per workgroup, 64 channels per blockIdx.y); the backward runs one chunk per workgroup (CPW = 1),
+// its waves side by side over the channels. wv is made provably uniform, so chunk, b, t0 and t1 live in SGPRs
+// (scalar address arithmetic). Lanes past Dx read channel Dx - 1's parameters (dd) and store nothing (valid).
+// scan_bwd_kernel takes the indices only: it holds A2 as packed state pairs, and its schedule at the 256-register
+// limit is sensitive to how they are formed.
+template <int CPW>
+struct ScanWave {
+  int lane, wv, chunk, b, d, dd, t0, t1;
+  bool valid;
+  float A2[SCAN_N], bias;   // A log2(e): the decays are exp2(dt A2); delta_bias
+  __device__ __forceinline__ ScanWave(const ScanArgs& a) {
+    lane = threadIdx.x & 63;
+    wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    chunk = CPW > 1 ? blockIdx.x * CPW + wv : blockIdx.x;
+    b = blockIdx.z;
+    d = CPW > 1 ? blockIdx.y * 64 + lane : blockIdx.y * blockDim.x + wv * 64 + lane;
+    valid = d < a.Dx;
+    dd = valid ? d : a.Dx - 1;
+    t0 = chunk * a.Tc;
+    t1 = min(a.L, t0 + a.Tc);
   }
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ void lds_row8(const float* p, float (&v)[SCAN_N]) {
-  const f32x4 lo = *(const f32x4*)p, hi = *(const f32x4*)(p + 4);
+  // the channel's parameters, loaded after a wave without a chunk has left
+  __device__ __forceinline__ void load_params(const ScanArgs& a) {
 #pragma unroll
-  for (int n = 0; n < 4; ++n) { v[n] = lo[n]; v[n + 4] = hi[n]; }
-}
+    for (int n = 0; n < SCAN_N; ++n) A2[n] = a.A[dd * SCAN_N + n] * LOG2E;
+    bias = a.dbias ? a.dbias[dd] : 0.f;
+  }
+  // this lane's 8 states in a (B, nch, Dx, N) workspace
+  __device__ __forceinline__ long long sidx(const ScanArgs& a) const {
+    return (((long long)b * a.nch + chunk) * a.Dx + dd) * SCAN_N;
+  }
+};
 
 // ---------------------------------------------------------------------------------- forward chunk pass
 // MODE 0: zero initial state -> xend, sdt. MODE 1: xinit -> y (+ checkpoints).
-// PFN: software-pipelined loads. Each group's u / dt loads are issued one group ahead and the next staging
+// The loads are software-pipelined: each group's u / dt loads are issued one group ahead and the next staging
 // block's B / C rows one block ahead (held in registers, written to LDS after the block). On gfx950 vmcnt counts
 // stores too, so without this the wait for a group's loads also waits for the previous group's y / checkpoint
 // stores, and the B / C staging load latency is exposed once per SB steps.
+// (scan_fwd_step takes the wave's A2 / bias / valid / d one by one: handed the ScanWave, the MODE 1 kernels compile to
+// another schedule, two VGPRs apart.)
 template <typename T, int MODE>
 __device__ __forceinline__ void scan_fwd_step(const ScanArgs& a, float (&x)[SCAN_N], const float (&A2)[SCAN_N],
                                               float bias, float Dd, float uv, float drv, const float* row, int t,
                                               bool valid, int d, T* ckb, const Col<T>& ycol, float& sumdt) {
-  if (MODE == 1 && a.write_ckpt && ((t & (CKPT - 1)) == 0) && valid) {
-    T* cp = (ckb + (long long)(t / CKPT) * a.Dx * SCAN_N) + d * SCAN_N;
-    if constexpr (sizeof(T) == 2) {   // bf16 I/O: bf16 checkpoints (one 16-B store; the backward recomputes from them)
-      bf16x8 v;
-#pragma unroll
-      for (int n = 0; n < SCAN_N; ++n) v[n] = to_bf16(x[n]);
-      *(bf16x8*)cp = v;
-    } else {
-      *(f32x4*)cp = f32x4{x[0], x[1], x[2], x[3]};
-      *(f32x4*)(cp + 4) = f32x4{x[4], x[5], x[6], x[7]};
-    }
-  }
-#if LCI_SCAN_PROBE
-  // transcendental-floor probe (timing only, wrong results): the same loads, softplus and 8 decay exps per
-  // channel-step; the state update is one add, the B / C rows, the dtu B product and the C x dot are dropped
-  {
-    const float dt = softplus(drv + bias);
-    float e[SCAN_N];
-    decay8(dt, A2, e);
-#pragma unroll
-    for (int n = 0; n < SCAN_N; ++n) x[n] += e[n];
-    (void)row; (void)uv; (void)Dd;
-    if (MODE == 1) ycol.st(t, x[0]);
-    else sumdt += dt;
-    return;
-  }
-#endif
+  // bf16 I/O: bf16 checkpoints (one 16-B store; the backward recomputes from them)
+  if (MODE == 1 && a.write_ckpt && ((t & (CKPT - 1)) == 0) && valid)
+    st8((ckb + (long long)(t / CKPT) * a.Dx * SCAN_N) + d * SCAN_N, x);
   float Bv[SCAN_N];
-  lds_row8(row, Bv);
+  ld8(row, Bv);
   const float dt = softplus(drv + bias);
   const float dtu = dt * uv;
   float e[SCAN_N];
@@ -214,7 +207,7 @@ __device__ __forceinline__ void scan_fwd_step(const ScanArgs& a, float (&x)[SCAN
   for (int n = 0; n < SCAN_N; ++n) x[n] = fmaf(e[n], x[n], dtu * Bv[n]);
   if (MODE == 1) {
     float Cv[SCAN_N];
-    lds_row8(row + 8, Cv);
+    ld8(row + SCAN_N, Cv);
     float y0 = Dd * uv, y1 = 0.f;
 #pragma unroll
     for (int n = 0; n < SCAN_N; n += 2) {
@@ -227,114 +220,78 @@ __device__ __forceinline__ void scan_fwd_step(const ScanArgs& a, float (&x)[SCAN
   }
 }
 
-template <typename T, int MODE, bool PFN>
+template <typename T, int MODE>
 __global__ __launch_bounds__(256) void scan_fwd_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) float bcl[4][SB * BCS];
-  // wave index made provably uniform: chunk / step indices then live in SGPRs (scalar address arithmetic)
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int chunk = blockIdx.x * 4 + wv;
-  const int b = blockIdx.z;
-  const int d = blockIdx.y * 64 + lane;
-  if (chunk >= a.nch) return;
-  const bool valid = d < a.Dx;
-  const int dd = valid ? d : a.Dx - 1;
-  float A2[SCAN_N], x[SCAN_N];
-#pragma unroll
-  for (int n = 0; n < SCAN_N; ++n) A2[n] = a.A[dd * SCAN_N + n] * LOG2E;
-  const float bias = a.dbias ? a.dbias[dd] : 0.f;
-  const float Dd = a.D ? a.D[dd] : 0.f;
-  const long long sidx = (((long long)b * a.nch + chunk) * a.Dx + dd) * SCAN_N;
+  ScanWave<4> w(a);
+  if (w.chunk >= a.nch) return;
+  w.load_params(a);
+  const int b = w.b, t0 = w.t0, t1 = w.t1;
+  float x[SCAN_N];
+  const float Dd = a.D ? a.D[w.dd] : 0.f;
+  const long long sidx = w.sidx(a);
 #pragma unroll
   for (int n = 0; n < SCAN_N; ++n) x[n] = MODE && !a.zero_carry ? a.xinit[sidx + n] : 0.f;
   // per-step addresses = wave-uniform row base (scalar arithmetic) + this lane's channel offset
-  const Col<T> ucol((const T*)a.u + b * a.bu, a.L, a.tu, a.Dx, d, valid);
-  const Col<T> dcol((const T*)a.delta + b * a.bd, a.L, a.td, a.Dx, d, valid);
-  const Col<T> ycol((T*)a.y + b * a.by, a.L, a.ty, a.Dx, d, valid);
+  const Col<T> ucol((const T*)a.u + b * a.bu, a.L, a.tu, a.Dx, w.d, w.valid);
+  const Col<T> dcol((const T*)a.delta + b * a.bd, a.L, a.td, a.Dx, w.d, w.valid);
+  const Col<T> ycol((T*)a.y + b * a.by, a.L, a.ty, a.Dx, w.d, w.valid);
   const T* Bp = (const T*)a.Bm + b * a.bB;
   const T* Cp = (const T*)a.Cm + b * a.bC;
   T* ckb = (T*)a.ckpt + (long long)b * a.nck * a.Dx * SCAN_N;
-  float* bc = bcl[wv];
-  const int t0 = chunk * a.Tc, t1 = min(a.L, t0 + a.Tc);
+  float* bc = bcl[w.wv];
   float sumdt = 0.f;
-  if constexpr (!PFN) {
-    for (int tsb = t0; tsb < t1; tsb += SB) {
-      stage_bc<T, MODE == 1>(a, bc, Bp, Cp, tsb, t1, lane);
-      const int tse = min(t1, tsb + SB);
-      for (int tb = tsb; tb < tse; tb += PF) {
-        float uf[PF], dr[PF];
+  // two register sets for the u / dt groups (even / odd group of the chunk) and one for the next B / C rows
+  float ua[PF], da[PF], ub[PF], db[PF];
+  auto load_group = [&](int tb, float (&uf)[PF], float (&dr)[PF]) {
 #pragma unroll
-        for (int i = 0; i < PF; ++i) {        // the group's u / dt loads first (clamped, branch-free)
-          const int t = min(tb + i, tse - 1);
-          uf[i] = ucol.ld(t);
-          dr[i] = dcol.ld(t);
-        }
-        const int nvalid = tse - tb;   // >= PF except in a chunk's ragged tail
+    for (int i = 0; i < PF; ++i) {
+      const int t = min(tb + i, t1 - 1);   // clamped, branch-free; past the chunk end the values are unused
+      uf[i] = ucol.ld(t);
+      dr[i] = dcol.ld(t);
+    }
+  };
+  auto run_group = [&](int tb, int tsb, const float (&uf)[PF], const float (&dr)[PF]) {
+    const int nvalid = t1 - tb;
 #pragma unroll
-        for (int i = 0; i < PF; ++i)
-          if (i < nvalid)
-            scan_fwd_step<T, MODE>(a, x, A2, bias, Dd, uf[i], dr[i], bc + (tb + i - tsb) * BCS, tb + i, valid, d,
-                                   ckb, ycol, sumdt);
+    for (int i = 0; i < PF; ++i)
+      if (i < nvalid)
+        scan_fwd_step<T, MODE>(a, x, w.A2, w.bias, Dd, uf[i], dr[i], bc + (tb + i - tsb) * BCS, tb + i, w.valid, w.d,
+                               ckb, ycol, sumdt);
+  };
+  Row8<T> rb, rc;
+  auto load_rows = [&](int tsb) {
+    const long long t = min(tsb + w.lane, t1 - 1);
+    rb.load(Bp + t * a.tB);
+    if constexpr (MODE == 1) rc.load(Cp + t * a.tC);
+  };
+  auto store_rows = [&]() {
+    float* dst = bc + w.lane * BCS;
+    st8(dst, rb);
+    if constexpr (MODE == 1) st8(dst + SCAN_N, rc);
+    __builtin_amdgcn_wave_barrier();
+  };
+  load_rows(t0);
+  load_group(t0, ua, da);
+  store_rows();
+  for (int tsb = t0; tsb < t1; tsb += SB) {
+    const int tse = min(t1, tsb + SB);
+    if (tse < t1) load_rows(tse);           // next block's rows, written to LDS after this block's steps
+    // SB / PF = 8 groups per block (even count): the two register sets alternate without copies
+    for (int tb = tsb; tb < tse; tb += 2 * PF) {
+      load_group(tb + PF, ub, db);
+      run_group(tb, tsb, ua, da);
+      if (tb + PF < tse) {
+        load_group(tb + 2 * PF, ua, da);
+        run_group(tb + PF, tsb, ub, db);
       }
     }
-  } else {
-    // two register sets for the u / dt groups (even / odd group of the chunk) and one for the next B / C rows
-    float ua[PF], da[PF], ub[PF], db[PF];
-    auto load_group = [&](int tb, float (&uf)[PF], float (&dr)[PF]) {
-#pragma unroll
-      for (int i = 0; i < PF; ++i) {
-        const int t = min(tb + i, t1 - 1);   // clamped, branch-free; past the chunk end the values are unused
-        uf[i] = ucol.ld(t);
-        dr[i] = dcol.ld(t);
-      }
-    };
-    auto run_group = [&](int tb, int tsb, const float (&uf)[PF], const float (&dr)[PF]) {
-      const int nvalid = t1 - tb;
-#pragma unroll
-      for (int i = 0; i < PF; ++i)
-        if (i < nvalid)
-          scan_fwd_step<T, MODE>(a, x, A2, bias, Dd, uf[i], dr[i], bc + (tb + i - tsb) * BCS, tb + i, valid, d,
-                                 ckb, ycol, sumdt);
-    };
-    Row8<T> rb, rc;
-    auto load_rows = [&](int tsb) {
-      const long long t = min(tsb + lane, t1 - 1);
-      rb.load(Bp + t * a.tB);
-      if constexpr (MODE == 1) rc.load(Cp + t * a.tC);
-    };
-    auto store_rows = [&]() {
-      float* dst = bc + lane * BCS;
-      *(f32x4*)dst = f32x4{rb[0], rb[1], rb[2], rb[3]};
-      *(f32x4*)(dst + 4) = f32x4{rb[4], rb[5], rb[6], rb[7]};
-      if constexpr (MODE == 1) {
-        *(f32x4*)(dst + 8) = f32x4{rc[0], rc[1], rc[2], rc[3]};
-        *(f32x4*)(dst + 12) = f32x4{rc[4], rc[5], rc[6], rc[7]};
-      }
-      __builtin_amdgcn_wave_barrier();
-    };
-    load_rows(t0);
-    load_group(t0, ua, da);
-    store_rows();
-    for (int tsb = t0; tsb < t1; tsb += SB) {
-      const int tse = min(t1, tsb + SB);
-      if (tse < t1) load_rows(tse);           // next block's rows, written to LDS after this block's steps
-      // SB / PF = 8 groups per block (even count): the two register sets alternate without copies
-      for (int tb = tsb; tb < tse; tb += 2 * PF) {
-        load_group(tb + PF, ub, db);
-        run_group(tb, tsb, ua, da);
-        if (tb + PF < tse) {
-          load_group(tb + 2 * PF, ua, da);
-          run_group(tb + PF, tsb, ub, db);
-        }
-      }
-      __builtin_amdgcn_wave_barrier();        // this block's LDS row reads precede the overwrite (wave-local)
-      if (tse < t1) store_rows();
-    }
+    __builtin_amdgcn_wave_barrier();        // this block's LDS row reads precede the overwrite (wave-local)
+    if (tse < t1) store_rows();
   }
-  if (MODE == 0 && valid) {
-    float* xe = a.xend + sidx;
-    *(f32x4*)xe = f32x4{x[0], x[1], x[2], x[3]};
-    *(f32x4*)(xe + 4) = f32x4{x[4], x[5], x[6], x[7]};
-    a.sdt[((long long)b * a.nch + chunk) * a.Dx + d] = sumdt;
+  if (MODE == 0 && w.valid) {
+    st8(a.xend + sidx, x);
+    a.sdt[((long long)b * a.nch + w.chunk) * a.Dx + w.d] = sumdt;
   }
 }
 
@@ -400,31 +357,24 @@ __global__ __launch_bounds__(64) void scan_carry_kernel(ScanArgs a) {
 template <typename T>
 __global__ __launch_bounds__(256) void scan_bwd_agg_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) float bcl[4][SB * BCS];
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int chunk = blockIdx.x * 4 + wv;
-  const int b = blockIdx.z;
-  const int d = blockIdx.y * 64 + lane;
-  if (chunk >= a.nch) return;
-  const bool valid = d < a.Dx;
-  const int dd = valid ? d : a.Dx - 1;
-  float A2[SCAN_N], g[SCAN_N];
+  ScanWave<4> w(a);
+  if (w.chunk >= a.nch) return;
+  w.load_params(a);
+  const int b = w.b, t0 = w.t0, t1 = w.t1;
+  float g[SCAN_N];
 #pragma unroll
-  for (int n = 0; n < SCAN_N; ++n) { A2[n] = a.A[dd * SCAN_N + n] * LOG2E; g[n] = 0.f; }
-  const float bias = a.dbias ? a.dbias[dd] : 0.f;
-  const Col<T> dcol((const T*)a.delta + b * a.bd, a.L, a.td, a.Dx, d, valid);
-  const Col<T> gcol((const T*)a.dy + b * a.bdy, a.L, a.tdy, a.Dx, d, valid);
+  for (int n = 0; n < SCAN_N; ++n) g[n] = 0.f;
+  const Col<T> dcol((const T*)a.delta + b * a.bd, a.L, a.td, a.Dx, w.d, w.valid);
+  const Col<T> gcol((const T*)a.dy + b * a.bdy, a.L, a.tdy, a.Dx, w.d, w.valid);
   const T* Cp = (const T*)a.Cm + b * a.bC;
-  float* bc = bcl[wv];
-  const int t0 = chunk * a.Tc, t1 = min(a.L, t0 + a.Tc);
-  // staging blocks of SB steps from the chunk's end; C_t rows go to LDS slots 8..15 (stage_bc's C slot)
+  float* bc = bcl[w.wv];
+  // staging blocks of SB steps from the chunk's end; C_t rows go to the rows' C slot (floats 8..15)
   for (int tsb = t0 + ((t1 - 1 - t0) / SB) * SB; tsb >= t0; tsb -= SB) {
     {
-      const long long t = min(tsb + lane, t1 - 1);
+      const long long t = min(tsb + w.lane, t1 - 1);
       Row8<T> rc;
       rc.load(Cp + t * a.tC);
-      float* dst = bc + lane * BCS;
-      *(f32x4*)(dst + 8) = f32x4{rc[0], rc[1], rc[2], rc[3]};
-      *(f32x4*)(dst + 12) = f32x4{rc[4], rc[5], rc[6], rc[7]};
+      st8(bc + w.lane * BCS + SCAN_N, rc);
       __builtin_amdgcn_wave_barrier();
     }
     const int tse = min(t1, tsb + SB);
@@ -440,11 +390,11 @@ __global__ __launch_bounds__(256) void scan_bwd_agg_kernel(ScanArgs a) {
       for (int i = 0; i < PF; ++i) {
         if (te - i >= tsb) {
           float Cv[SCAN_N];
-          lds_row8(bc + (te - i - tsb) * BCS + 8, Cv);
-          const float dt = softplus(dr[i] + bias);
-          const float gy = valid ? gyv[i] : 0.f;
+          ld8(bc + (te - i - tsb) * BCS + SCAN_N, Cv);
+          const float dt = softplus(dr[i] + w.bias);
+          const float gy = w.valid ? gyv[i] : 0.f;
           float e[SCAN_N];
-          decay8(dt, A2, e);
+          decay8(dt, w.A2, e);
 #pragma unroll
           for (int n = 0; n < SCAN_N; ++n) g[n] = e[n] * fmaf(Cv[n], gy, g[n]);
         }
@@ -452,11 +402,7 @@ __global__ __launch_bounds__(256) void scan_bwd_agg_kernel(ScanArgs a) {
     }
     __builtin_amdgcn_wave_barrier();
   }
-  if (valid) {
-    float* o = a.gl + (((long long)b * a.nch + chunk) * a.Dx + d) * SCAN_N;
-    *(f32x4*)o = f32x4{g[0], g[1], g[2], g[3]};
-    *(f32x4*)(o + 4) = f32x4{g[4], g[5], g[6], g[7]};
-  }
+  if (w.valid) st8(a.gl + w.sidx(a), g);
 }
 
 template <int CTRL>
@@ -520,16 +466,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   constexpr int NP = SCAN_N / 2;   // state pairs
   __shared__ float red[SB][2 * SCAN_N];
   __shared__ __attribute__((aligned(16))) float bcs[SB][BCS];
-  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int chunk = blockIdx.x, b = blockIdx.z;
-  const int d = blockIdx.y * blockDim.x + wv * 64 + lane;
-  const bool valid = d < a.Dx;
-  const int dd = valid ? d : a.Dx - 1;
+  const ScanWave<1> w(a);
+  const int tid = threadIdx.x, lane = w.lane, chunk = w.chunk, b = w.b, d = w.d, dd = w.dd, t0 = w.t0, t1 = w.t1;
+  const bool valid = w.valid;
   const bool single = blockDim.x == 64;
   for (int i = tid; i < SB * 2 * SCAN_N; i += blockDim.x) (&red[0][0])[i] = 0.f;
   f32x2 A2[NP], h[NP], dA[NP];
   {
-    const float* gi = a.gin + (((long long)b * a.nch + chunk) * a.Dx + dd) * SCAN_N;
+    const float* gi = a.gin + w.sidx(a);
 #pragma unroll
     for (int k = 0; k < NP; ++k) {
       A2[k] = f32x2{a.A[dd * SCAN_N + 2 * k], a.A[dd * SCAN_N + 2 * k + 1]} * LOG2E;
@@ -548,7 +492,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const T* Bp = (const T*)a.Bm + b * a.bB;
   const T* Cp = (const T*)a.Cm + b * a.bC;
   const T* ckb = (const T*)a.ckpt + (long long)b * a.nck * a.Dx * SCAN_N;
-  const int t0 = chunk * a.Tc, t1 = min(a.L, t0 + a.Tc);
   const int nsb = (t1 - t0 + CKPT - 1) / CKPT;
   // per-lane operands of one sub-block, loaded a sub-block ahead (invalid lanes read zeros)
   float nck[SCAN_N], nu[CKPT], nd[CKPT], ng[CKPT];
@@ -564,32 +507,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   load_lane(t0 + (nsb - 1) * CKPT);
   int blk0 = -1;   // first step of the staged block
+  // the staged block's dB/dC sums to dBC (stored where this workgroup is an entry's only writer); rezero: red is
+  // cleared for the next block
+  auto flush = [&](bool rezero) {
+    __syncthreads();
+    for (int k = tid; k < SB * 2 * SCAN_N; k += blockDim.x) {
+      const int i = k / (2 * SCAN_N), j = k % (2 * SCAN_N);
+      const int t = blk0 + i;
+      float* dst = a.dBC + ((long long)b * a.L + t) * (2 * SCAN_N) + j;
+      if (t < t1) {
+        if (a.dbc_plain) *dst = red[i][j];
+        else atomicAdd(dst, red[i][j]);
+      }
+      if (rezero) red[i][j] = 0.f;
+    }
+  };
   for (int sb = nsb - 1; sb >= 0; --sb) {
     const int s0 = t0 + sb * CKPT;
     if (blk0 < 0 || s0 < blk0) {   // new staging block [blk0, blk0 + SB) holding s0 (uniform branch)
-      if (blk0 >= 0) {             // flush the finished block's dB/dC sums
-        __syncthreads();
-        for (int k = tid; k < SB * 2 * SCAN_N; k += blockDim.x) {
-          const int i = k / (2 * SCAN_N), j = k % (2 * SCAN_N);
-          const int t = blk0 + i;
-          float* dst = a.dBC + ((long long)b * a.L + t) * (2 * SCAN_N) + j;
-          if (t < t1) {
-            if (a.dbc_plain) *dst = red[i][j];
-            else atomicAdd(dst, red[i][j]);
-          }
-          red[i][j] = 0.f;
-        }
-      }
+      if (blk0 >= 0) flush(true);   // the finished block's dB/dC sums
       blk0 = t0 + ((s0 - t0) / SB) * SB;
       if (tid < SB) {
         const long long t = min(blk0 + tid, t1 - 1);
         Row8<T> rb, rc;
         rb.load(Bp + t * a.tB);
         rc.load(Cp + t * a.tC);
-        *(f32x4*)&bcs[tid][0] = f32x4{rb[0], rb[1], rb[2], rb[3]};
-        *(f32x4*)&bcs[tid][4] = f32x4{rb[4], rb[5], rb[6], rb[7]};
-        *(f32x4*)&bcs[tid][8] = f32x4{rc[0], rc[1], rc[2], rc[3]};
-        *(f32x4*)&bcs[tid][12] = f32x4{rc[4], rc[5], rc[6], rc[7]};
+        st8(&bcs[tid][0], rb);
+        st8(&bcs[tid][SCAN_N], rc);
       }
       __syncthreads();
     }
@@ -659,16 +603,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
     }
   }
-  __syncthreads();
-  for (int k = tid; k < SB * 2 * SCAN_N; k += blockDim.x) {
-    const int i = k / (2 * SCAN_N), j = k % (2 * SCAN_N);
-    const int t = blk0 + i;
-    float* dst = a.dBC + ((long long)b * a.L + t) * (2 * SCAN_N) + j;
-    if (t < t1) {
-      if (a.dbc_plain) *dst = red[i][j];
-      else atomicAdd(dst, red[i][j]);
-    }
-  }
+  flush(false);
   if constexpr (PARTIALS) {
     if (!valid) return;
     const long long o = (((long long)b * a.nch + chunk) * a.Dx + d) * SCAN_N;
@@ -714,8 +649,7 @@ __global__ __launch_bounds__(256) void scan_param_reduce_kernel(ScanArgs a) {
 // ------------------------------------------------------------------------------ depthwise conv + SiLU
 // in (B, L, 2C) (x | z halves, channels-last), w (C, 3) x2, 'same' padding (1 left, 1 right).
 // out_x (B, L, C) and out_z written at column offset zoff of a (B, L, oz_ts) buffer.
-// A thread owns one channel of the 2C and a run of CONV_T tokens (lanes = consecutive channels: coalesced
-// rows); the 3-tap window slides in registers, weight-gradient partials stay in registers until one atomic.
+// The 3-tap window slides in registers; the weight-gradient partial sums stay in registers until the run's end.
 constexpr int CONV_K = 3;
 constexpr int CONV_T = 256;
 
@@ -728,77 +662,14 @@ struct ConvArgs {
   int B, L, C, in_ts, ox_ts, oz_ts, zoff;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void dwconv_silu_fwd_kernel(ConvArgs a) {
-  const int cc = blockIdx.x * 256 + threadIdx.x;
-  if (cc >= 2 * a.C) return;
-  const int b = blockIdx.z, t0 = blockIdx.y * CONV_T, t1 = min(a.L, t0 + CONV_T);
-  const int half = cc / a.C, c = cc % a.C;
-  const float* w = (half ? a.wz : a.wx) + c * CONV_K;
-  const float* bp = half ? a.bz : a.bx;
-  const float w0 = w[0], w1 = w[1], w2 = w[2], bias = bp ? bp[c] : 0.f;
-  const T* in = (const T*)a.in + (long long)b * a.L * a.in_ts + cc;
-  auto X = [&](int s) -> float { return (s >= 0 && s < a.L) ? (float)in[(long long)s * a.in_ts] : 0.f; };
-  float xm = X(t0 - 1), x0 = X(t0);
-  for (int t = t0; t < t1; ++t) {
-    const float xp = X(t + 1);
-    const float pre = fmaf(w0, xm, fmaf(w1, x0, fmaf(w2, xp, bias)));
-    const float sv = pre / (1.f + __expf(-pre));
-    if (half == 0) ((T*)a.ox)[((long long)b * a.L + t) * a.ox_ts + c] = (T)sv;
-    else ((T*)a.oz)[((long long)b * a.L + t) * a.oz_ts + a.zoff + c] = (T)sv;
-    xm = x0; x0 = xp;
-  }
-}
-
-// g(s) = dout(s) * silu'(pre(s)); din(t) = w0 g(t+1) + w1 g(t) + w2 g(t-1); dw[j] += g(t) x(t+j-1)
-template <typename T>
-__global__ __launch_bounds__(256) void dwconv_silu_bwd_kernel(ConvArgs a) {
-  const int cc = blockIdx.x * 256 + threadIdx.x;
-  if (cc >= 2 * a.C) return;
-  const int b = blockIdx.z, t0 = blockIdx.y * CONV_T, t1 = min(a.L, t0 + CONV_T);
-  const int half = cc / a.C, c = cc % a.C;
-  const float* w = (half ? a.wz : a.wx) + c * CONV_K;
-  const float* bp = half ? a.bz : a.bx;
-  const float w0 = w[0], w1 = w[1], w2 = w[2], bias = bp ? bp[c] : 0.f;
-  const T* in = (const T*)a.in + (long long)b * a.L * a.in_ts + cc;
-  const T* go = half ? (const T*)a.gz + (long long)b * a.L * a.oz_ts + a.zoff + c
-                     : (const T*)a.gx + (long long)b * a.L * a.ox_ts + c;
-  const int gts = half ? a.oz_ts : a.ox_ts;
-  auto X = [&](int s) -> float { return (s >= 0 && s < a.L) ? (float)in[(long long)s * a.in_ts] : 0.f; };
-  auto G = [&](int s, float xm, float x0, float xp) -> float {
-    if (s < 0 || s >= a.L) return 0.f;
-    const float pre = fmaf(w0, xm, fmaf(w1, x0, fmaf(w2, xp, bias)));
-    const float sg = 1.f / (1.f + __expf(-pre));
-    return (float)go[(long long)s * gts] * sg * fmaf(pre, 1.f - sg, 1.f);
-  };
-  // window over x: x(t-2) .. x(t+2); g(t-1), g(t), g(t+1)
-  float xa = X(t0 - 2), xb = X(t0 - 1), xc = X(t0), xd = X(t0 + 1);
-  float gm = G(t0 - 1, xa, xb, xc), g0 = G(t0, xb, xc, xd);
-  float dw0 = 0.f, dw1 = 0.f, dw2 = 0.f, db = 0.f;
-  T* din = (T*)a.din + (long long)b * a.L * a.in_ts + cc;
-  for (int t = t0; t < t1; ++t) {
-    const float xe = X(t + 2);
-    const float gp = G(t + 1, xc, xd, xe);
-    din[(long long)t * a.in_ts] = (T)fmaf(w0, gp, fmaf(w1, g0, w2 * gm));
-    dw0 = fmaf(g0, xb, dw0);
-    dw1 = fmaf(g0, xc, dw1);
-    dw2 = fmaf(g0, xd, dw2);
-    db += g0;
-    xa = xb; xb = xc; xc = xd; xd = xe;
-    gm = g0; g0 = gp;
-  }
-  const int nrun = (a.L + CONV_T - 1) / CONV_T;
-  float* pp = a.part + (((long long)b * nrun + blockIdx.y) * 2 * a.C + cc) * 4;
-  *(f32x4*)pp = f32x4{dw0, dw1, dw2, db};
-}
-
-// ---------------------------------------------------------------- depthwise conv + SiLU, 16-byte vector path
-// A thread owns V = 16 / sizeof(T) adjacent channels (one 16-byte vector of a token row; never straddling the x / z
-// halves since C % V == 0) and a run of CONV_T tokens; adjacent threads take adjacent vectors, so a wave's row
-// accesses are 16 bytes per lane instead of 2. Rows are loaded CONV_U tokens ahead of their use.
+// A thread owns V adjacent channels (one vector of a token row, never straddling the x / z halves since C % V == 0)
+// and a run of CONV_T tokens; adjacent threads take adjacent vectors. V = 16 / sizeof(T) in the forward (16 bytes
+// per lane instead of 2) and 4 in the backward where C, the column offsets, the token strides and the base pointers
+// allow it; V = 1, one channel per thread, is the fallback for every other layout. Rows are loaded CONV_U tokens
+// ahead of their use.
 constexpr int CONV_U = 4;
 
-// V channels of one token row as a T vector of V lanes (16 B: 8 bf16 / 4 f32; 8 B: 4 bf16)
+// V channels of one token row as a T vector of V lanes (16 B: 8 bf16 / 4 f32; 8 B: 4 bf16; V = 1: one element)
 template <typename T, int V>
 struct VecN {
   typedef T raw __attribute__((ext_vector_type(V)));
@@ -814,7 +685,7 @@ struct VecN {
   }
 };
 
-template <typename T, int V, int TR = CONV_T>
+template <typename T, int V>
 struct ConvVecCtx {
   typedef typename VecN<T, V>::raw raw;
   int b, t0, t1, c, cc0;
@@ -823,11 +694,11 @@ struct ConvVecCtx {
     const int G = 2 * a.C / V;                      // vectors per token row
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const int run = (int)(idx / G), g = (int)(idx % G);
-    const int nrun = (a.L + TR - 1) / TR;
+    const int nrun = (a.L + CONV_T - 1) / CONV_T;
     b = blockIdx.z;
     ok = run < nrun;
-    t0 = run * TR;
-    t1 = min(a.L, t0 + TR);
+    t0 = run * CONV_T;
+    t1 = min(a.L, t0 + CONV_T);
     cc0 = g * V;
     zhalf = cc0 >= a.C;
     c = zhalf ? cc0 - a.C : cc0;
@@ -879,15 +750,14 @@ __global__ __launch_bounds__(256) void dwconv_silu_fwd_vec_kernel(ConvArgs a) {
   }
 }
 
+// g(s) = dout(s) * silu'(pre(s)); din(t) = w0 g(t+1) + w1 g(t) + w2 g(t-1); dw[j] += g(t) x(t+j-1)
 // Weight / bias gradients: every (sequence, run of CONV_T tokens, channel) writes its (dw0, dw1, dw2, db) partial
 // sums to a workspace the caller reduces (deterministic). The float atomics this replaced were serialised by the L2
 // per address: at the Swin-window shapes (8192 sequences of 64 tokens) 2 * 10^5 threads x 16 atomics onto 384
 // addresses took 0.5 ms per call, and they had forced 1024-token runs (a short grid) at long L.
-constexpr int CONV_TB = CONV_T;
-
 template <typename T, int V>
 __global__ __launch_bounds__(256) void dwconv_silu_bwd_vec_kernel(ConvArgs a) {
-  const ConvVecCtx<T, V, CONV_TB> ctx(a);
+  const ConvVecCtx<T, V> ctx(a);
   typedef VecN<T, V> Vec;
   typedef typename Vec::raw raw;
   if (!ctx.ok) return;
@@ -958,8 +828,8 @@ __global__ __launch_bounds__(256) void dwconv_silu_bwd_vec_kernel(ConvArgs a) {
       }
     }
   }
-  const int nrun = (a.L + CONV_TB - 1) / CONV_TB;
-  float* pp = a.part + (((long long)ctx.b * nrun + ctx.t0 / CONV_TB) * 2 * a.C + ctx.cc0) * 4;
+  const int nrun = (a.L + CONV_T - 1) / CONV_T;
+  float* pp = a.part + (((long long)ctx.b * nrun + ctx.t0 / CONV_T) * 2 * a.C + ctx.cc0) * 4;
 #pragma unroll
   for (int v = 0; v < V; ++v) *(f32x4*)(pp + 4 * v) = f32x4{dw0[v], dw1[v], dw2[v], db[v]};
 }
@@ -967,6 +837,15 @@ __global__ __launch_bounds__(256) void dwconv_silu_bwd_vec_kernel(ConvArgs a) {
 }  // namespace lci
 
 using namespace lci;
+
+// The bf16 / f32 choice of every launch below: f(tag) with tag::type the I/O element type of `dtype`
+// (1: bf16, otherwise f32; lci.h)
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F>
+static void with_dtype(int dtype, F&& f) {
+  if (dtype == 1) f(TypeTag<bf16>{});
+  else f(TypeTag<float>{});
+}
 
 static int scan_fill(ScanArgs& a, int B, int L, int Dx, int N, int Tc) {
   LCI_CHECK(N == SCAN_N, "selective_scan: d_state %d unsupported (8)", N);
@@ -1018,17 +897,11 @@ extern "C" int lci_selective_scan_fwd(int dtype, const void* u, const void* delt
   a.zero_carry = one;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((a.nch + 3) / 4, (Dx + 63) / 64, B);
-  // LCI_SCAN_PF=0: the forward passes without the software-pipelined loads (A/B hook)
-  static const bool pf = !getenv("LCI_SCAN_PF") || atoi(getenv("LCI_SCAN_PF")) != 0;
   auto chunk_pass = [&](auto mode) {
-    constexpr int M = decltype(mode)::value;
-    if (dtype == 1) {
-      if (pf) hipLaunchKernelGGL((scan_fwd_kernel<bf16, M, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((scan_fwd_kernel<bf16, M, false>), grid, dim3(256), 0, s, a);
-    } else {
-      if (pf) hipLaunchKernelGGL((scan_fwd_kernel<float, M, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((scan_fwd_kernel<float, M, false>), grid, dim3(256), 0, s, a);
-    }
+    with_dtype(dtype, [&](auto t) {
+      typedef typename decltype(t)::type T;
+      hipLaunchKernelGGL((scan_fwd_kernel<T, decltype(mode)::value>), grid, dim3(256), 0, s, a);
+    });
   };
   if (!one) {
     chunk_pass(std::integral_constant<int, 0>{});
@@ -1041,19 +914,14 @@ extern "C" int lci_selective_scan_fwd(int dtype, const void* u, const void* delt
   return 0;
 }
 
-static int scan_bwd_waves(int Tc, int Dx) {
-  static const int wenv = getenv("LCI_SCAN_BWD_WAVES") ? atoi(getenv("LCI_SCAN_BWD_WAVES")) : 0;
-  const int wmax = wenv > 0 ? wenv : (Tc >= 512 ? 1 : 4);
-  return std::max(1, std::min(std::min(wmax, 4), (Dx + 63) / 64));
-}
+static int scan_bwd_waves(int Tc, int Dx) { return std::max(1, std::min(Tc >= 512 ? 1 : 4, (Dx + 63) / 64)); }
 
 // 1: lci_selective_scan_bwd stores every dBC entry exactly once at this shape (one workgroup per (b, chunk) holds
 // all Dx channels), so dBC needs no zero fill; 0: it accumulates into dBC with atomics.
 extern "C" int lci_selective_scan_bwd_plain_dbc(int L, int Dx, int chunk) {
   (void)L;
-  static const bool off = getenv("LCI_SCAN_PLAIN_DBC") && atoi(getenv("LCI_SCAN_PLAIN_DBC")) == 0;   // A/B hook
   const int nwv = scan_bwd_waves(chunk, Dx);
-  return !off && (Dx + nwv * 64 - 1) / (nwv * 64) == 1;
+  return (Dx + nwv * 64 - 1) / (nwv * 64) == 1;
 }
 
 // dA (Dx*N), dD (Dx), ddelta_bias (Dx) are accumulated (caller zeroes them); dBC (B, L, 2N) too, except where
@@ -1079,8 +947,9 @@ extern "C" int lci_selective_scan_bwd(int dtype, const void* u, const void* delt
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((a.nch + 3) / 4, (Dx + 63) / 64, B);
   if (!a.zero_carry) {
-    if (dtype == 1) hipLaunchKernelGGL((scan_bwd_agg_kernel<bf16>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_agg_kernel<float>), grid, dim3(256), 0, s, a);
+    with_dtype(dtype, [&](auto t) {
+      hipLaunchKernelGGL((scan_bwd_agg_kernel<typename decltype(t)::type>), grid, dim3(256), 0, s, a);
+    });
     LCI_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_carry_kernel<true>, dim3(Dx, B), dim3(64), 0, s, a);
     LCI_LAUNCH_CHECK();
@@ -1089,23 +958,20 @@ extern "C" int lci_selective_scan_bwd(int dtype, const void* u, const void* delt
   // (2 waves per SIMD) 3-wave groups leave 2 of a CU's 8 wave slots empty and two SIMDs with one wave each, so
   // long chunks run one wave per workgroup (L=2^21: 7.8 -> 6.6 ms); short chunks keep the shared staging, whose
   // per-token dB/dC flush (one set of global atomics per workgroup and token) dominates there (L=65536, Tc=64:
-  // 0.60 ms at 4 waves vs 0.80 at 1). LCI_SCAN_BWD_WAVES overrides.
+  // 0.60 ms at 4 waves vs 0.80 at 1).
   const int nwv = scan_bwd_waves(a.Tc, Dx);
   dim3 gridc(a.nch, (Dx + nwv * 64 - 1) / (nwv * 64), B);
   a.dbc_plain = lci_selective_scan_bwd_plain_dbc(L, Dx, a.Tc);
   // parameter gradients: the B * nch float atomics per address from the waves' ends serialise in L2 (the dwconv
   // backward's lesson): short chunks write partials and sum them in one more launch (L=65536: 0.60 -> 0.42 ms).
   // Long chunks keep the atomics: there the partials build of the kernel measured slower (8.6 vs 6.9 ms at L=2^21,
-  // a main-loop schedule change at 256 VGPRs). LCI_SCAN_PARAM_PARTIALS = 0 / 1 overrides.
-  static const int penv = getenv("LCI_SCAN_PARAM_PARTIALS") ? atoi(getenv("LCI_SCAN_PARAM_PARTIALS")) : -1;
-  const bool partials = penv >= 0 ? penv != 0 : a.Tc < 512;
-  if (partials) {
-    if (dtype == 1) hipLaunchKernelGGL((scan_bwd_kernel<bf16, true>), gridc, dim3(nwv * 64), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_kernel<float, true>), gridc, dim3(nwv * 64), 0, s, a);
-  } else {
-    if (dtype == 1) hipLaunchKernelGGL((scan_bwd_kernel<bf16, false>), gridc, dim3(nwv * 64), 0, s, a);
-    else hipLaunchKernelGGL((scan_bwd_kernel<float, false>), gridc, dim3(nwv * 64), 0, s, a);
-  }
+  // a main-loop schedule change at 256 VGPRs).
+  const bool partials = a.Tc < 512;
+  with_dtype(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (partials) hipLaunchKernelGGL((scan_bwd_kernel<T, true>), gridc, dim3(nwv * 64), 0, s, a);
+    else hipLaunchKernelGGL((scan_bwd_kernel<T, false>), gridc, dim3(nwv * 64), 0, s, a);
+  });
   LCI_LAUNCH_CHECK();
   if (partials) {
     const int ny = std::max(1, std::min(64, (B * a.nch) / 16));
@@ -1115,13 +981,12 @@ extern "C" int lci_selective_scan_bwd(int dtype, const void* u, const void* delt
   return 0;
 }
 
-// The 16-byte vector kernels need C a multiple of the vector width and 16-byte aligned rows of every operand;
-// LCI_DWCONV_VEC=0 forces the scalar kernels (A/B hook).
+// The V-channel kernels need C and the z column offset multiples of V, and V-element aligned rows of every operand
+// (base pointers and token strides); anything else runs one channel per thread (V = 1).
 static bool dwconv_vec_ok(int dtype, int V, int C, const void* const* ptrs, int np, const int* tss, int nts,
                           int zoff) {
-  static const bool on = !getenv("LCI_DWCONV_VEC") || atoi(getenv("LCI_DWCONV_VEC")) != 0;
   const int vb = V * (dtype == 1 ? 2 : 4);   // vector bytes
-  if (!on || C % V || zoff % V) return false;
+  if (C % V || zoff % V) return false;
   for (int i = 0; i < np; ++i)
     if (ptrs[i] && ((uintptr_t)ptrs[i] % vb)) return false;
   for (int i = 0; i < nts; ++i)
@@ -1129,8 +994,8 @@ static bool dwconv_vec_ok(int dtype, int V, int C, const void* const* ptrs, int 
   return true;
 }
 
-static dim3 dwconv_vec_grid(int V, int B, int L, int C, int TR = CONV_T) {
-  const long long threads = (long long)((L + TR - 1) / TR) * (2 * C / V);
+static dim3 dwconv_vec_grid(int V, int B, int L, int C) {
+  const long long threads = (long long)((L + CONV_T - 1) / CONV_T) * (2 * C / V);
   return dim3((unsigned)((threads + 255) / 256), 1, B);
 }
 
@@ -1143,16 +1008,16 @@ extern "C" int lci_dwconv_silu_fwd(int dtype, const void* in, const float* wx, c
   a.B = B; a.L = L; a.C = C; a.in_ts = in_ts; a.ox_ts = ox_ts; a.oz_ts = oz_ts; a.zoff = zoff;
   const void* vp[] = {in, ox, oz};
   const int vt[] = {in_ts, ox_ts, oz_ts};
-  if (dwconv_vec_ok(dtype, dtype == 1 ? 8 : 4, C, vp, 3, vt, 3, zoff)) {
-    const dim3 gv = dwconv_vec_grid(dtype == 1 ? 8 : 4, B, L, C);
-    if (dtype == 1) hipLaunchKernelGGL((dwconv_silu_fwd_vec_kernel<bf16, 8>), gv, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((dwconv_silu_fwd_vec_kernel<float, 4>), gv, dim3(256), 0, (hipStream_t)stream, a);
-    LCI_LAUNCH_CHECK();
-    return 0;
-  }
-  dim3 grid((2 * C + 255) / 256, (L + CONV_T - 1) / CONV_T, B);
-  if (dtype == 1) hipLaunchKernelGGL(dwconv_silu_fwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(dwconv_silu_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  // forward: one 16-byte vector per thread and token (8 bf16 / 4 f32 channels)
+  const bool vec = dwconv_vec_ok(dtype, dtype == 1 ? 8 : 4, C, vp, 3, vt, 3, zoff);
+  with_dtype(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    constexpr int V = 16 / sizeof(T);
+    if (vec) hipLaunchKernelGGL((dwconv_silu_fwd_vec_kernel<T, V>), dwconv_vec_grid(V, B, L, C), dim3(256), 0,
+                                (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((dwconv_silu_fwd_vec_kernel<T, 1>), dwconv_vec_grid(1, B, L, C), dim3(256), 0,
+                            (hipStream_t)stream, a);
+  });
   LCI_LAUNCH_CHECK();
   return 0;
 }
@@ -1172,24 +1037,19 @@ extern "C" int lci_dwconv_silu_bwd(int dtype, const void* in, const float* wx, c
   a.in = in; a.wx = wx; a.bx = bx; a.wz = wz; a.bz = bz; a.gx = gx; a.gz = gz; a.din = din;
   a.part = part;
   a.B = B; a.L = L; a.C = C; a.in_ts = in_ts; a.ox_ts = ox_ts; a.oz_ts = oz_ts; a.zoff = zoff;
-  // backward: 4 channels per thread (8-byte bf16 / 16-byte f32 vectors). The 8-channel bf16 version holds 16
-  // windows' state in 182 VGPRs (2 waves per SIMD) and measured slower than the scalar kernels (3.5 vs 2.6 ms at
-  // B=1, L=2^21, 2C=384). LCI_DWCONV_BWD_V = 0 (scalar) / 4 / 8 overrides.
-  static const int bwd_v = getenv("LCI_DWCONV_BWD_V") ? atoi(getenv("LCI_DWCONV_BWD_V")) : 4;
+  // backward: 4 channels per thread (8-byte bf16 / 16-byte f32 vectors). An 8-channel bf16 version held 16 windows'
+  // state in 182 VGPRs (2 waves per SIMD) and measured slower than one channel per thread (3.5 vs 2.6 ms at B=1,
+  // L=2^21, 2C=384; profiles/r02_dwconv_vec_ab.txt).
   const void* vp[] = {in, gx, gz, din};
   const int vt[] = {in_ts, ox_ts, oz_ts};
-  const int V = dtype == 1 ? bwd_v : std::min(bwd_v, 4);
-  if (V > 0 && dwconv_vec_ok(dtype, V, C, vp, 4, vt, 3, zoff)) {
-    const dim3 gv = dwconv_vec_grid(V, B, L, C, CONV_TB);
-    if (dtype != 1) hipLaunchKernelGGL((dwconv_silu_bwd_vec_kernel<float, 4>), gv, dim3(256), 0, (hipStream_t)stream, a);
-    else if (V == 8) hipLaunchKernelGGL((dwconv_silu_bwd_vec_kernel<bf16, 8>), gv, dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((dwconv_silu_bwd_vec_kernel<bf16, 4>), gv, dim3(256), 0, (hipStream_t)stream, a);
-    LCI_LAUNCH_CHECK();
-    return 0;
-  }
-  dim3 grid((2 * C + 255) / 256, (L + CONV_T - 1) / CONV_T, B);
-  if (dtype == 1) hipLaunchKernelGGL(dwconv_silu_bwd_kernel<bf16>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(dwconv_silu_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  const bool vec = dwconv_vec_ok(dtype, 4, C, vp, 4, vt, 3, zoff);
+  with_dtype(dtype, [&](auto t) {
+    typedef typename decltype(t)::type T;
+    if (vec) hipLaunchKernelGGL((dwconv_silu_bwd_vec_kernel<T, 4>), dwconv_vec_grid(4, B, L, C), dim3(256), 0,
+                                (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((dwconv_silu_bwd_vec_kernel<T, 1>), dwconv_vec_grid(1, B, L, C), dim3(256), 0,
+                            (hipStream_t)stream, a);
+  });
   LCI_LAUNCH_CHECK();
   return 0;
 }

@@ -74,10 +74,16 @@ def test_selective_scan_chunked_long(L, d, dtype, tol):
 
 
 @pytest.mark.parametrize("dtype,L,C,bias", [(torch.float32, 700, 96, False), (torch.float32, 257, 96, True),
-                                             (torch.bfloat16, 1000, 192, True), (torch.bfloat16, 513, 36, False)])
+                                             (torch.bfloat16, 1000, 192, True), (torch.bfloat16, 513, 36, False),
+                                             (torch.float32, 259, 37, True), (torch.bfloat16, 259, 37, False),
+                                             (torch.float32, 1, 6, False), (torch.bfloat16, 3, 40, True),
+                                             (torch.bfloat16, 256, 36, True)])
 def test_dwconv_silu_pair(dtype, L, C, bias):
     """mamba.py:118-119 conv1d(k=3, 'same', groups=C) + SiLU on both halves: vector forward when C % V == 0 (V = 4 f32 /
-    8 bf16; C=36 bf16 takes the scalar forward), 4-channel vector backward; runs across the 256-token boundary."""
+    8 bf16), 4-channel vector backward when C % 4 == 0, otherwise the one-channel-per-thread fallback (C = 36 bf16:
+    fallback forward, 4-channel backward; C = 37 and 6: fallback both ways). Runs across the 256-token boundary (257,
+    259, ...) and ending exactly on it (256); L = 1 has both halo rows outside the sequence, L = 3 is shorter than the
+    vector kernels' 4-row prefetch."""
     from long_context_biomedical_imaging_amd import kernels
     torch.manual_seed(0)
     B = 2
@@ -104,6 +110,76 @@ def test_dwconv_silu_pair(dtype, L, C, bias):
     assert rel_err(wxc.grad, wxr.grad) < 10 * tol and rel_err(wzc.grad, wzr.grad) < 10 * tol
     if bias:
         assert rel_err(bxc.grad, bxr.grad) < 10 * tol and rel_err(bzc.grad, bzr.grad) < 10 * tol
+
+
+def _guarded(vals, B, L, ts, off, lead):
+    """A NaN-filled flat buffer holding a (B, L, ts) view `lead` elements in, with `vals` (B, L, w) at columns
+    off .. off+w-1 (vals None: left NaN, an output to be written). Returns (flat, view, mask of the data elements)."""
+    w = vals.shape[-1] if torch.is_tensor(vals) else vals[0]
+    dtype = vals.dtype if torch.is_tensor(vals) else vals[1]
+    n = B * L * ts
+    assert off + w <= ts   # the last row's data ends inside the view: every kernel access stays below lead + n
+    flat = torch.full((lead + n + 64,), float("nan"), device="cuda", dtype=dtype)
+    view = flat[lead:lead + n].view(B, L, ts)
+    mask = torch.zeros_like(flat, dtype=torch.bool)
+    mask[lead:lead + n].view(B, L, ts)[..., off:off + w] = True
+    if torch.is_tensor(vals):
+        view[..., off:off + w] = vals
+    return flat, view, mask
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)
+
+
+def dwconv_direct(dtype, strided, B=2, L=261, C=40):
+    """lci_dwconv_silu_fwd / _bwd through _lib.call on guarded buffers. strided=False: contiguous rows (token strides
+    2C, C, 2C, z at column C), every base 16-byte aligned: the vector kernels. strided=True: the same values with
+    token strides 2C+3 / C+1 / 2C+5, z at column C+1 and every base one element past a 16-byte boundary: the dispatch
+    must take the fallback. Every element outside the data columns is NaN before the calls (pad columns, the x-half
+    columns of the oz / gz buffers, a band of >= 64 elements either side) and must be bitwise unchanged after them; the
+    outputs' data columns must hold no NaN (nothing read from a pad). Returns the data columns."""
+    from long_context_biomedical_imaging_amd import _lib
+    g = torch.Generator().manual_seed(11)
+    xz = torch.randn(B, L, 2 * C, generator=g).to(dtype).cuda()
+    gx = torch.randn(B, L, C, generator=g).to(dtype).cuda()
+    gz = torch.randn(B, L, C, generator=g).to(dtype).cuda()
+    wx, wz = torch.randn(C, 3, generator=g).cuda(), torch.randn(C, 3, generator=g).cuda()
+    bx, bz = torch.randn(C, generator=g).cuda(), torch.randn(C, generator=g).cuda()
+    in_ts, ox_ts, oz_ts, zoff, lead = (2 * C + 3, C + 1, 2 * C + 5, C + 1, 65) if strided else (2 * C, C, 2 * C, C, 64)
+    bufs = {"in": _guarded(xz, B, L, in_ts, 0, lead), "gx": _guarded(gx, B, L, ox_ts, 0, lead),
+            "gz": _guarded(gz, B, L, oz_ts, zoff, lead), "ox": _guarded((C, dtype), B, L, ox_ts, 0, lead),
+            "oz": _guarded((C, dtype), B, L, oz_ts, zoff, lead), "din": _guarded((2 * C, dtype), B, L, in_ts, 0, lead)}
+    rows = int(_lib.load().lci_dwconv_silu_bwd_part_rows(B, L))
+    # part must be 16-byte aligned in either call (the entry point checks it): 64 f32 of band keep it so
+    bufs["part"] = _guarded((2 * C * 4, torch.float32), 1, rows, 2 * C * 4, 0, 64)
+    before = {k: _bits(f).clone() for k, (f, _, _) in bufs.items()}
+    p = {k: v.data_ptr() for k, (_, v, _) in bufs.items()}
+    assert all((p[k] % 16 != 0) == strided for k in p if k != "part") and p["part"] % 16 == 0
+    dt, st = _lib.DTYPE[dtype], _lib.stream_of(xz)
+    _lib.call("lci_dwconv_silu_fwd", dt, p["in"], wx.data_ptr(), bx.data_ptr(), wz.data_ptr(), bz.data_ptr(), p["ox"],
+              p["oz"], B, L, C, 3, in_ts, ox_ts, oz_ts, zoff, st)
+    _lib.call("lci_dwconv_silu_bwd", dt, p["in"], wx.data_ptr(), bx.data_ptr(), wz.data_ptr(), bz.data_ptr(), p["gx"],
+              p["gz"], p["din"], p["part"], B, L, C, 3, in_ts, ox_ts, oz_ts, zoff, st)
+    torch.cuda.synchronize()
+    out = {}
+    for k, (flat, _, mask) in bufs.items():
+        assert torch.equal(_bits(flat)[~mask], before[k][~mask]), f"{k}: a pad or guard element was written"
+        if k in ("ox", "oz", "din", "part"):
+            out[k] = flat[mask].clone()
+            assert not torch.isnan(out[k]).any(), f"{k}: NaN in the output (a pad was read, or an element not written)"
+    return out
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+def test_dwconv_silu_paths_agree_bitwise(dtype):
+    """The vector kernels (contiguous, aligned) and the fallback (odd token strides, z at an odd column, misaligned
+    bases) on the same values, B 2, L 261, C 40: ox, the z half, din and the per-run (dw, db) partials are equal bit
+    for bit (the per-channel arithmetic has one order in both, and a part row is one run's sequential sum), and no
+    pad, x-half column or guard band is read or written (dwconv_direct)."""
+    vec, fb = dwconv_direct(dtype, False), dwconv_direct(dtype, True)
+    for k in ("ox", "oz", "din", "part"):
+        assert vec[k].shape == fb[k].shape and torch.equal(_bits(vec[k]), _bits(fb[k])), k
 
 
 @pytest.mark.parametrize("amp", [False, True])
