@@ -199,7 +199,7 @@ int lci_conv3_fwd(const void* x, const void* w, void* y, int B, int D, int H, in
 /* Split-K form for small volumes (few 512-voxel tiles): part (nsplit, B*D*H*W, Cout) f32 workspace holds the
  * partial sums of contiguous ranges of the (tap group, 32-channel chunk) slabs, summed in split order into y
  * (deterministic). nsplit = lci_conv3_fwd_splits(B*D*H*W, Cin, Cout, KD) (1: use lci_conv3_fwd); Cin % 32 == 0;
- * y and part 16-byte aligned. */
+ * nsplit <= KD * 3 * (Cin / 32), one slab per split at the least; y and part 16-byte aligned. */
 int lci_conv3_fwd_splits(long long V, int Cin, int Cout, int KD);
 /* The kernels' weight operands from the f32 parameter w (Cout, Cin, KD*3*3) (nn.Conv layout), one pass:
  * mode 0: (Cout, T, Cin) bf16 for lci_conv3_fwd; mode 1: (Cin_pad, T, Cout) bf16 = w[n][c][T-1-t] (the flipped,

@@ -1233,6 +1233,10 @@ static int conv3_fwd_impl(const void* x, const void* w, void* y, float* part, in
   LCI_CHECK(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)y & (nsplit > 1 ? 15 : 7)) == 0 &&
                 ((uintptr_t)part & 15) == 0, "conv3: misaligned pointers");
   LCI_CHECK(nsplit >= 1 && (nsplit == 1 || Cin % 32 == 0), "conv3: split-K needs Cin %% 32 == 0");
+  // every split owns at least one (tap group, 32-channel chunk) slab: a workgroup with an empty slab range would
+  // still issue the DMA of its first slab, possibly one past the last, and leave without waiting for it
+  LCI_CHECK(nsplit == 1 || nsplit <= KD * 3 * (Cin / 32), "conv3: nsplit (%d) exceeds the %d slabs", nsplit,
+            KD * 3 * (Cin / 32));
   ConvArgs a{};
   a.x = (const bf16*)x; a.w = (const bf16*)w; a.y = (bf16*)y;
   a.V = (long long)B * D * H * W;

@@ -1,6 +1,7 @@
 """Host checks of the decoder-head convolution plumbing (no GPU): the flat row-shift weight-gradient algebra
 of kernels._conv3_wgrad and the GEMM forms of the kernel==stride transposed conv and the 1x1 conv, against
-torch's own fp32 convolutions (the MONAI-1.3 get_conv_layer semantics: padding (k - s + 1) // 2)."""
+torch's own fp32 convolutions (the MONAI-1.3 get_conv_layer semantics: padding (k - s + 1) // 2); the pin of the
+fp64 references of tests/test_conv_kernel_gpu.py against torch in fp64, and lci_conv3_fwd_splits against its rule."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -22,6 +23,78 @@ def test_conv3_wgrad_row_shift(B, S, Cin, Cout):
     dw = kernels._conv3_wgrad(x_cl, dy_cl, 3 if nd == 3 else 1)
     assert dw.shape == ref.shape
     assert torch.allclose(dw.double(), ref, atol=1e-4, rtol=1e-4)
+
+
+@pytest.mark.parametrize("B,S,KD,Cin,Cout", [(2, (3, 4, 5), 3, 64, 3), (1, (1, 6, 7), 1, 32, 5),
+                                            (2, (1, 5, 1), 3, 32, 2), (1, (2, 3, 2), 3, 5, 4)])
+def test_conv_kernel_reference_is_pinned_by_torch(B, S, KD, Cin, Cout):
+    """The fp64 sums over taps of tests/test_conv_kernel_gpu.py (forward with its per-slab contributions, data
+    gradient, weight gradient per voxel split) against F.conv3d / F.conv2d and autograd in fp64."""
+    from test_conv_kernel_gpu import _reference, _reference_dgrad, _reference_wgrad
+    g = torch.Generator().manual_seed(5)
+    T = KD * 9
+    x = torch.randn(B, *S, Cin, generator=g, dtype=torch.float64)
+    w = torch.randn(Cout, Cin, T, generator=g, dtype=torch.float64)
+    dy = torch.randn(B, *S, Cout, generator=g, dtype=torch.float64)
+
+    def conv(xx, ww):   # channels-last in and out; the weight in torch's (Cout, Cin, kd, kh, kw) / (Cout, Cin, kh, kw)
+        if KD == 1:
+            y2 = F.conv2d(xx[:, 0].permute(0, 3, 1, 2), ww.reshape(Cout, Cin, 3, 3), padding=1)
+            return y2.permute(0, 2, 3, 1)[:, None]
+        return F.conv3d(xx.permute(0, 4, 1, 2, 3), ww.reshape(Cout, Cin, 3, 3, 3), padding=1).permute(0, 2, 3, 4, 1)
+
+    xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+    yr = conv(xr, wr)
+    (yr * dy).sum().backward()
+    close = lambda a, b: torch.testing.assert_close(a, b.detach(), rtol=1e-11, atol=1e-12)  # noqa: E731
+    close(_reference(x, w, KD), yr)
+    close(_reference_dgrad(dy, w, KD), xr.grad)
+    V, W = B * S[0] * S[1] * S[2], S[2]
+    ns, Lv = 3, -(-(V // W) * (W + 1) // 3)
+    parts = _reference_wgrad(x, dy, KD, ns, Lv)                       # (ns, T, Cout, Cin)
+    close(parts.sum(0).permute(1, 2, 0), wr.grad)
+    sid, G = [], 0                                                    # the split of every voxel, line by line
+    for _ in range(V // W):
+        sid += [(G + i) // Lv for i in range(W)]
+        G += W + 1                                                    # one gap row after every line
+    sid = torch.tensor(sid).reshape(B, *S, 1)
+    for s in range(ns):
+        wr.grad = None
+        (conv(x, wr) * dy * (sid == s)).sum().backward()
+        close(parts[s].permute(1, 2, 0), wr.grad)
+    if Cin % 32 == 0:
+        y, per = _reference(x, w, KD, slabs=True)
+        close(per.sum(0), yr)
+        nch = Cin // 32
+        for sl in range(per.shape[0]):                                # slab sl: tap row grp = (kd, kh), 32 channels
+            grp, ch = divmod(sl, nch)
+            wm = torch.zeros_like(w).reshape(Cout, Cin, KD * 3, 3)
+            wm[:, 32 * ch:32 * ch + 32, grp] = w.reshape(Cout, Cin, KD * 3, 3)[:, 32 * ch:32 * ch + 32, grp]
+            close(per[sl], conv(x, wm.reshape(Cout, Cin, T)))
+
+
+@pytest.mark.parametrize("V,Cin,Cout,KD", [
+    (512 * 255, 32, 32, 3), (512 * 256, 32, 32, 3), (512 * 127 + 1, 64, 64, 3),   # the nb >= 256 cut-off, either side
+    (630, 64, 32, 3), (64, 768, 768, 3), (585, 32, 96, 1),                        # the nslab / 2 cap (9, 108 -> 64, 1)
+    (64, 2048, 32, 3), (8, 4096, 64, 1),                                          # the cap of 64 splits
+    (51200, 768, 96, 3), (40000, 1024, 256, 3),                                   # the 100 MB cap
+    (4096, 96, 96, 3), (32768, 256, 128, 3),                                      # 512 / nb decides
+    (630, 16, 32, 3), (630, 32, 48, 3), (630, 32, 32, 2), (0, 32, 32, 3)])        # not split at all
+def test_conv3_fwd_splits_rule(V, Cin, Cout, KD):
+    """lci_conv3_fwd_splits (host arithmetic) against the restatement of its rule in tests/test_conv_kernel_gpu.py."""
+    from long_context_biomedical_imaging_amd import _lib
+    from test_conv_kernel_gpu import _expected_fwd_splits
+    assert _lib.load().lci_conv3_fwd_splits(V, Cin, Cout, KD) == _expected_fwd_splits(V, Cin, Cout, KD)
+
+
+def test_conv3_fwd_splits_rule_landmarks():
+    """The restatement itself at values worked out by hand, so that it cannot drift together with the library."""
+    from test_conv_kernel_gpu import _expected_fwd_splits as e
+    assert e(512 * 255, 32, 32, 3) == 3 and e(512 * 256, 32, 32, 3) == 1     # nb 255: ceil(512 / 255) = 3; nb 256: none
+    assert e(630, 64, 32, 3) == 9                                           # 18 slabs / 2
+    assert e(64, 2048, 32, 3) == 64                                         # 576 slabs: the cap of 64
+    assert e(51200, 768, 96, 3) == 5                                        # nb 100 -> 6 splits = 118 MB -> 5 = 98 MB
+    assert e(4096, 96, 96, 3) == 13                                         # nb 8: 512 / 8 = 64, 27 slabs / 2 = 13
 
 
 def test_gemm_forms_match_torch_convs():

@@ -50,8 +50,8 @@ def test_conv3_parity(B, S, Cin, Cout):
 def test_conv3_split_k_small_volumes(S, Cin, Cout):
     """Small volumes (the 4^3 - 16^3 SwinUNETR stages) take the split-K form (lci_conv3_fwd_split: f32 partials of
     slab ranges, summed in split order): forward, data and weight gradients vs the fp32 conv on the host, and the
-    split forward vs the unsplit kernel (LCI_CONV_SPLITK=0) within bf16 output rounding."""
-    import os
+    split forward vs the unsplit kernel (lci_conv3_fwd called directly on the same channels-last operands) within
+    bf16 output rounding."""
     torch.manual_seed(2)
     assert kernels._lib.load().lci_conv3_fwd_splits(S[0] * S[1] * S[2], Cin, Cout, 3) > 1
     x = torch.randn(1, Cin, *S).bfloat16().float()
@@ -66,11 +66,13 @@ def test_conv3_split_k_small_volumes(S, Cin, Cout):
     y.backward(dy.cuda().bfloat16())
     assert rel_err(xc.grad.float(), xr.grad) < 1e-2
     assert rel_err(wc.grad, wr.grad) < 1e-2
-    os.environ["LCI_CONV_SPLITK"] = "0"
-    try:
-        y1 = kernels.conv3(x.cuda(), w.cuda())
-    finally:
-        del os.environ["LCI_CONV_SPLITK"]
+    x_cl = kernels._to_cl(x.cuda(), 3)
+    wp = kernels._conv3_pack(w.cuda(), 3, 0, Cin)
+    y1 = torch.full((1, *S, Cout), float("nan"), device="cuda", dtype=torch.bfloat16)
+    kernels._lib.call("lci_conv3_fwd", x_cl.data_ptr(), wp.data_ptr(), y1.data_ptr(), 1, *S, Cin, Cout, 3,
+                      kernels._lib.stream_of(x_cl))
+    y1 = kernels._from_cl(y1, 3)
+    assert rel_err(y1.float(), yr) < 1e-2
     assert rel_err(y.float(), y1.float()) < 4e-3
 
 
