@@ -79,8 +79,8 @@ extern "C" {
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
  * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile;
  * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef; 39: lci_class_*;
- * 40: lci_augment (+ _ws_bytes). */
-#define LCI_ABI_VERSION 40
+ * 40: lci_augment (+ _ws_bytes); 41: lci_attn_bwd_variant2, lci_attn_bwd_dkdv_pick. */
+#define LCI_ABI_VERSION 41
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -131,6 +131,18 @@ int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, const void*
 /* The dQ kernel lci_attn_bwd runs for a shape on a device of n_cu compute units (0 / 1 as above): the rule of
  * lci_attn_fwd_pick (pure host arithmetic). */
 int lci_attn_bwd_dq_pick(int B, int L, int H, int n_cu);
+/* lci_attn_bwd_variant with the split of the dK/dV pass forced as well: dkdv_wide_wgs = W > 0 runs
+ * attn_bwd_dkdv_hs3_kernel (96 keys per wave, 384 per workgroup) on keys [0, 384 W) and attn_bwd_dkdv_hs_kernel (64
+ * keys per wave) on the rest (384 (W - 1) < L); 0 = the 64-key kernel alone; -1 = what lci_attn_bwd does: the choice
+ * of lci_attn_bwd_dkdv_pick for the current device. dK, dV and dQ are bitwise the same for every W. */
+int lci_attn_bwd_variant2(int dq_variant, int dkdv_wide_wgs, int stage, const void* qkv, const void* out,
+                          const void* dout, const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H,
+                          int head_dim, float scale, void* stream);
+/* W of lci_attn_bwd for a shape on a device of n_cu compute units (pure host arithmetic): among the splits whose two
+ * grids (B H W workgroups of 384 keys; B H ceil((L - 384 W) / 256) of 256 keys, or none) each pass lci_attn_fwd_pick's
+ * rule, the one with the fewest rounds weighted 3 (wide) : 2 (narrow), the larger W on a tie, if that is no more than
+ * the 64-key kernel alone takes; otherwise 0. B H = 12, L = 65536, 256 units: 128. */
+int lci_attn_bwd_dkdv_pick(int B, int L, int H, int n_cu);
 
 /* ViT attention in exact f32 products (csrc/attention_gen.hip): the reference's fp32 (non-AMP) SABlock path
  * (backbone_vit.py:191-201: fp32 einsums + softmax) and head dims 65..256 (the `custom` preset,

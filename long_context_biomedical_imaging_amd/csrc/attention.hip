@@ -15,7 +15,9 @@
 //            same O and lse2.
 // Backward:  (1) attn_bwd_delta_kernel: delta = rowsum(dO*O), written with -lse2 as the chains' row constants;
 //            (2) attn_bwd_dkdv_hs_kernel: 64 keys per wave on the lane, sweeps query tiles: S, dP recomputed,
-//            dV^T += dO^T.P, dK^T += Q^T.dS; (3) attn_bwd_dq_hs_kernel: 64 queries per wave, sweeps key tiles:
+//            dV^T += dO^T.P, dK^T += Q^T.dS; where both grids still fill the chip (lci_attn_bwd_dkdv_pick: the metric
+//            shape) the first 384 W keys go to attn_bwd_dkdv_hs3_kernel instead: the same stream with 96 keys per
+//            wave, two thirds of the LDS reads per MFMA, bitwise the same dK and dV; (3) attn_bwd_dq_hs_kernel: 64 queries per wave, sweeps key tiles:
 //            S^T, dP^T, dQ^T += K^T.dS^T; where the grid still fills the chip (lci_attn_bwd_dq_pick, the forward's rule)
 //            attn_bwd_dq_hs4_kernel instead: 128 queries per wave on one shared softmax shift per lane, half the
 //            K | V staging, LDS reads and barriers per MFMA (workgroups whose lse2 spread forbids the shared shift
@@ -46,6 +48,7 @@ struct AttnArgs {
   int H, L;
   float c;                                         // scale * log2(e)
   float scale;
+  int k0;                                          // bwd dkdv kernel: first key of its grid (keys below: the wide kernel's)
 };
 
 // Per-64-key-tile bound on |k|: knorm[b][h][t] = max_{key in tile t} ||k_key||_2 (f32 of the bf16 keys).
@@ -181,6 +184,11 @@ __device__ __forceinline__ void hs_vmcnt() {   // s_waitcnt vmcnt(N), lgkmcnt / 
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(A), "a"(B), "v"(C))
 #define HS_MFMA_C(d, A, B) \
   asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(A), "a"(B))
+// the same with B in arch VGPRs (attn_bwd_dkdv_hs3_kernel: its third key block's fragments, the AGPR half being full)
+#define HS_MFMA_C0V(d, A, B, C) \
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(A), "v"(B), "v"(C))
+#define HS_MFMA_CV(d, A, B) \
+  asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(A), "v"(B))
 
 // s_waitcnt lgkmcnt(0) with vmcnt / expcnt left at their maxima (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] |
 // lgkmcnt[11:8] | vmcnt[15:14])
@@ -212,7 +220,7 @@ __device__ __forceinline__ void hs_for_gaps(F&& f, std::integer_sequence<int, G.
   (f(std::integral_constant<int, G>{}), ...);
 }
 
-// ---- what the five placed kernels share. These helpers only compute values: where a kernel waits (hs_vmcnt) and
+// ---- what the six placed kernels share. These helpers only compute values: where a kernel waits (hs_vmcnt) and
 // where it moves fragments to AGPRs (HS_TO_AGPR) is part of its measured build and stays written in the kernel. The
 // register allocation of a placed loop follows the order of the prologue's statements, down to independent ones, and
 // the form the compiler sees them in before inlining: a helper keeps the statements it replaced, in their order
@@ -331,7 +339,7 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
   const int hh = blockIdx.y, b = blockIdx.z;
   const int L = a.L;
   const int h = lane >> 5, r32 = lane & 31;
-  const int kw0 = blockIdx.x * (HS_NW * 64) + wave * 64;
+  const int kw0 = a.k0 + blockIdx.x * (HS_NW * 64) + wave * 64;
   const int nqt = (L + KT - 1) / KT;
 
   // K^T / V^T as B operands: lane holds K[kw0 + 32kb + r32][16ks + 8h + j] (K prescaled into the exp2 domain)
@@ -675,6 +683,352 @@ __global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs_kernel(AttnArg
           }
           *(bf16x4*)(dkp + 32 * db + 8 * g + 4 * h) = k4;
           *(bf16x4*)(dvp + 32 * db + 8 * g + 4 * h) = v4;
+        }
+    }
+  }
+}
+
+// ------------------------------------------------- backward: dK, dV kernel, 96 keys per wave (three key blocks)
+// attn_bwd_dkdv_hs_kernel's stream with a third key block per wave: a workgroup owns 4 x 96 = 384 keys, and every Q /
+// dO fragment read from LDS feeds three key blocks. Per 32-query half 48 MFMAs against the narrow kernel's 32 LDS
+// reads, staging and barrier: 0.67 LDS reads per MFMA instead of 1. Per key the operations and their order over the
+// queries are the narrow kernel's, so dK and dV are bitwise the same.
+// Six segments of 8 gaps per half p; block kb's chains, its VALU (two segments) and its products follow each other as
+// in the narrow kernel, the three blocks two segments apart:
+//   seg A: chains kb0 (p)          || VALU kb2 (p-1) elements 8-15
+//   seg B: dV^T / dK^T kb2 (p-1)   || VALU kb0 elements 0-7   | LDS: dO^T / Q^T of half p (gaps 2-7)
+//   seg C: chains kb1              || VALU kb0 elements 8-15  | LDS: dO^T / Q^T (gaps 0-1)
+//   seg D: dV^T / dK^T kb0         || VALU kb1 elements 0-7
+//   seg E: chains kb2              || VALU kb1 elements 8-15  | LDS: Q rows of p+1, -lse2, dO rows (the narrow seg C)
+//   seg F: dV^T / dK^T kb1         || VALU kb2 elements 0-7   | LDS: -lse2, -delta, dO rows (the narrow seg D)
+// Registers: the 192 accumulators and the K / V fragments of blocks 0 and 1 fill the AGPR half (256); block 2's
+// fragments live in the arch half, which has room for them because
+//   - only two blocks' S / dP and packs are live at a time: block kb of half p uses set (kb & 1) ^ (p & 1) (block 2
+//     takes over block 0's set two segments after block 0's last pack, block 0 of the next half block 1's);
+//   - one set of transposed fragments serves all three blocks: fragment f is last read by block 2's products at
+//     seg B gap f of the next half and refilled at gap f + 2, four gaps or more before block 0's products read it.
+// Ring, prologue, ragged last tile, barrier and the 4-tile unroll are the narrow kernel's; the tiles arrive by LDS-DMA
+// (no register is left for staging). Staging reads reach tile nqt + 1: rows below L + 3 KT, inside the bound attn_check
+// sets for every placed kernel.
+constexpr int DKV3_KWG = HS_NW * 96;   // keys per workgroup
+__global__ __launch_bounds__(HS_NW * 64, 1) void attn_bwd_dkdv_hs3_kernel(AttnArgs a) {
+  constexpr int RC_B = 2 * KT * 4;                  // -lse2[64] | -delta[64] of one tile
+  constexpr int NOPS = 5;                           // LDS-DMA operations per wave and tile (prologue)
+  __shared__ __attribute__((aligned(16))) char smem[HS_NSLOT * HS_SLOT_B + HS_NSLOT * RC_B];
+  char* const rcs = smem + HS_NSLOT * HS_SLOT_B;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hh = blockIdx.y, b = blockIdx.z;
+  const int L = a.L;
+  const int h = lane >> 5, r32 = lane & 31;
+  const int kw0 = blockIdx.x * DKV3_KWG + wave * 96;
+  const int nqt = (L + KT - 1) / KT;
+
+  // K^T / V^T as B operands: lane holds K[kw0 + 32kb + r32][16ks + 8h + j] (K prescaled into the exp2 domain)
+  bf16x8 kf[3][4], vf[3][4];
+  {
+    const bf16* kp = a.k + b * a.bs_k + hh * a.hs;
+    const bf16* vp = a.v + b * a.bs_v + hh * a.hs;
+#pragma unroll
+    for (int kb = 0; kb < 3; ++kb) {
+      hs_load_b2(kf[kb], vf[kb], kp, a.rs_k, vp, a.rs_v, kw0 + 32 * kb + r32, L, h, a.c);
+    }
+  }
+  // the K / V loads complete here (as the narrow kernel)
+  hs_vmcnt<0>();
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    HS_TO_AGPR(kf[0][j]); HS_TO_AGPR(vf[0][j]);
+    HS_TO_AGPR(kf[1][j]); HS_TO_AGPR(vf[1][j]);
+    HS_OPAQUE(kf[2][j]); HS_OPAQUE(vf[2][j]);
+  }
+
+  // ---- prologue staging by LDS-DMA (as the narrow kernel)
+  const int rs2q = a.rs_q * 2, rs2d = a.rs_do * 2;
+  const rsrc_t rq = hs_rows_rsrc(a.q + b * a.bs_q + hh * a.hs, rs2q, L);
+  const rsrc_t rd = hs_rows_rsrc(a.dout + b * a.bs_do + hh * a.hs, rs2d, L);
+  const rsrc_t rr = make_rsrc(a.delta + ((long long)b * a.H + hh) * 2 * L + (wave & 1) * L, (uint32_t)L * 4);
+  const HsRing ring = hs_ring(rq, rs2q, rd, rs2d, lane, wave, smem);
+  const unsigned lds0 = ring.lds0;
+  auto dma_op = [&](int t, int i) __attribute__((always_inline)) {   // operation i (0-4) of tile t
+    if (i < 4) ring.dma(t, i);
+    if (i == 4) hs_dma4(rr, lane * 4, t * KT * 4,
+                        lds0 + (unsigned)(HS_NSLOT * HS_SLOT_B + (t & (HS_NSLOT - 1)) * RC_B + (wave & 1) * KT * 4));
+  };
+  // ---- fragment readers: the narrow kernel's 9 lane registers, everything else a DS immediate
+  unsigned q_off[4], t_off[2][2], rc_off;   // [k-step] | [d block][part] | row constants: + 16 h
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    q_off[ks] = 2 * sw128(r32, 16 * ks + 8 * h);
+    HS_OPAQUE(q_off[ks]);
+  }
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int part = 0; part < 2; ++part) {
+      t_off[db][part] = 2 * sw128(4 * h + ((lane & 15) >> 2) + 8 * part, 32 * db + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
+      HS_OPAQUE(t_off[db][part]);
+    }
+  rc_off = HS_NSLOT * HS_SLOT_B + 16 * h;   // (past the 64-KB ring: in the register, the rest is an immediate)
+  HS_OPAQUE(rc_off);
+  auto qrow = [&](int soff, int r0, int ks) __attribute__((always_inline)) {
+    return *(const bf16x8*)(smem + q_off[ks] + (soff + 2 * DH * r0));
+  };
+  auto trf = [&](int soff, int r0, int S, int db) __attribute__((always_inline)) {
+    const int imm = soff + 2 * DH * (r0 + 16 * S);
+    return cat44(lds_tr4((const bf16*)(smem + t_off[db][0] + imm)), lds_tr4((const bf16*)(smem + t_off[db][1] + imm)));
+  };
+  auto rcblk = [&](const char* rcslot, int which, int r0) __attribute__((always_inline)) {
+    const float* rc = (const float*)(rcslot + which * KT * 4) + r0 + 4 * h;
+    f32x16 r;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 v = *(const f32x4*)(rc + 8 * g);
+      r[4 * g] = v[0]; r[4 * g + 1] = v[1]; r[4 * g + 2] = v[2]; r[4 * g + 3] = v[3];
+    }
+    return r;
+  };
+
+  f32x16 dv[2][3], dk[2][3];   // [d block][key block]: dV^T / dK^T, lane = key, rows d = 32db + (i&3) + 8(i>>2) + 4h
+  f32x16 S[2], P[2];           // [set]: S~ - lse2 and dP - delta of a block's current half
+  f32x16 NLs, NDs;             // row constants (-lse2, -delta) of the chains' half
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    S[i] = P[i] = f32x16{};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dv[i][j] = dk[i][j] = f32x16{};
+  }
+  u32x4 pk[2][2] = {}, dd[2][2] = {};    // [set][k-step] bf16 P / dS packs (dword j = elements 2j, 2j+1)
+  bf16x8 tdo[2][2] = {}, tq[2][2] = {};  // [d block][k-step] transposed dO / Q fragments of the products' half
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    HS_OPAQUE(S[i]);
+    HS_OPAQUE(P[i]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      HS_TO_AGPR(dv[i][j]);
+      HS_TO_AGPR(dk[i][j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      HS_OPAQUE(pk[i][j]);
+      HS_OPAQUE(dd[i][j]);
+      HS_OPAQUE(tdo[i][j]);
+      HS_OPAQUE(tq[i][j]);
+    }
+  }
+  bf16x8 qa[4], da[4];                   // Q / dO row fragments of the chains' half
+
+  // VALU of gap g of a segment over elements 8e..8e+7 of set st, finishing set pst's elements 8pe..8pe+7 at gaps 0-2
+  // (the narrow kernel's valu_gap)
+  auto valu_gap = [&](int g, int st, int e, int pst, int pe) __attribute__((always_inline)) {
+    f32x16& s = S[st];
+    f32x16& p = P[st];
+    const int o = 8 * e, po = 8 * pe;
+    HS_EXP(s[o + g]);
+    if (g >= 2) HS_MUL(p[o + g - 2], s[o + g - 2]);
+    if (g == 0) HS_MUL(P[pst][po + 6], S[pst][po + 6]);
+    if (g == 1) HS_MUL(P[pst][po + 7], S[pst][po + 7]);
+    switch (g) {
+      case 0: HS_CVT(pk[pst][pe][3], S[pst][po + 6], S[pst][po + 7]); break;
+      case 1: HS_CVT(dd[pst][pe][2], P[pst][po + 4], P[pst][po + 5]); break;
+      case 2: HS_CVT(dd[pst][pe][3], P[pst][po + 6], P[pst][po + 7]); break;
+      case 3: HS_CVT(pk[st][e][0], s[o], s[o + 1]); break;
+      case 4: HS_CVT(pk[st][e][1], s[o + 2], s[o + 3]); break;
+      case 5: HS_CVT(dd[st][e][0], p[o], p[o + 1]); break;
+      case 6: HS_CVT(pk[st][e][2], s[o + 4], s[o + 5]); break;
+      default: HS_CVT(dd[st][e][1], p[o + 2], p[o + 3]); break;
+    }
+  };
+  // MFMA of gap g of a chain segment (S chain at gaps 0-3, dP chain at gaps 4-7) for key block kb into set st
+  auto chain_gap = [&](int g, int kb, int st) __attribute__((always_inline)) {
+    if (kb < 2) {
+      if (g == 0) HS_MFMA_C0(S[st], qa[0], kf[kb][0], NLs);
+      else if (g < 4) HS_MFMA_C(S[st], qa[g], kf[kb][g]);
+      else if (g == 4) HS_MFMA_C0(P[st], da[0], vf[kb][0], NDs);
+      else HS_MFMA_C(P[st], da[g - 4], vf[kb][g - 4]);
+    } else {
+      if (g == 0) HS_MFMA_C0V(S[st], qa[0], kf[2][0], NLs);
+      else if (g < 4) HS_MFMA_CV(S[st], qa[g], kf[2][g]);
+      else if (g == 4) HS_MFMA_C0V(P[st], da[0], vf[2][0], NDs);
+      else HS_MFMA_CV(P[st], da[g - 4], vf[2][g - 4]);
+    }
+  };
+  // MFMA of gap g of a gradient segment for key block kb with pack set st: (k-step s2, d block db, dV | dK)
+  auto grad_gap = [&](int g, int kb, int st) __attribute__((always_inline)) {
+    const int s2 = g >> 2, db = (g >> 1) & 1;
+    const bf16x8 pb = __builtin_bit_cast(bf16x8, pk[st][s2]);
+    const bf16x8 db8 = __builtin_bit_cast(bf16x8, dd[st][s2]);
+    if (g & 1) HS_MFMA_G(dk[db][kb], tq[db][s2], db8);
+    else HS_MFMA_G(dv[db][kb], tdo[db][s2], pb);
+  };
+  // transposed fragment f (gradient order: k-step f >> 2, d block (f >> 1) & 1, dO^T | Q^T) of rows r0: the
+  // operand of gap f of every gradient segment
+  auto tr_load = [&](int f, int soff, int r0) __attribute__((always_inline)) {
+    const int s2 = f >> 2, db = (f >> 1) & 1;
+    if (f & 1) tq[db][s2] = trf(soff, r0, s2, db);
+    else tdo[db][s2] = trf(soff + HS_TILE_B, r0, s2, db);
+  };
+  auto rc_load = [&](f32x16& r, int rcoff, int which, int r0, int g) __attribute__((always_inline)) {
+    const f32x4 v = *(const f32x4*)(smem + rc_off + (rcoff + which * KT * 4 + 4 * (r0 + 8 * g)));
+    r[4 * g] = v[0]; r[4 * g + 1] = v[1]; r[4 * g + 2] = v[2]; r[4 * g + 3] = v[3];
+  };
+
+  // One half-tile p = rows r0 of `slot`, parity C; segs E / F read half p+1 = rows nr0 of `nslot`. LDS reads one per
+  // gap (two at seg E gaps 6-7), each at least two gaps after the last MFMA read of the registers it refills (seven
+  // wait states for a row-constant block read as an MFMA C operand).
+  auto half = [&](auto CUR, int slot, int r0, int nslot, int nrc, int nr0, auto mid, auto sgap)
+      __attribute__((always_inline)) {
+    constexpr int X = decltype(CUR)::value, Y = X ^ 1;   // sets of blocks 0, 2 | of block 1 and of block 2 of half p-1
+    // seg A: chains kb0 || VALU kb2 (p-1) elements 8-15 (finishing its elements 0-7)
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      chain_gap(g, 0, X);
+      valu_gap(g, Y, 1, Y, 0);
+      sgap(0, g);
+    }
+    mid();
+    // seg B: dV / dK kb2 (p-1) || VALU kb0 elements 0-7 (finishing kb2 8-15)
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      grad_gap(g, 2, Y);
+      valu_gap(g, X, 0, Y, 1);
+      if (g >= 2) tr_load(g - 2, slot, r0);
+      sgap(1, g);
+    }
+    // seg C: chains kb1 || VALU kb0 elements 8-15
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      chain_gap(g, 1, Y);
+      valu_gap(g, X, 1, X, 0);
+      if (g < 2) tr_load(6 + g, slot, r0);
+      sgap(2, g);
+    }
+    // seg D: dV / dK kb0 || VALU kb1 elements 0-7 (finishing kb0 8-15)
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      grad_gap(g, 0, X);
+      valu_gap(g, Y, 0, X, 1);
+      sgap(3, g);
+    }
+    // seg E: chains kb2 (block 0's set) || VALU kb1 elements 8-15
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      chain_gap(g, 2, X);
+      valu_gap(g, Y, 1, Y, 0);
+      if (g == 2) HS_KEEP(NLs);
+      if (g == 6) HS_KEEP(NDs);
+      if (g >= 2 && g < 6) qa[g - 2] = qrow(nslot, nr0, g - 2);
+      if (g >= 6) {
+        rc_load(NLs, nrc, 0, nr0, g - 6);
+        da[g - 6] = qrow(nslot + HS_TILE_B, nr0, g - 6);
+      }
+      sgap(4, g);
+    }
+    // seg F: dV / dK kb1 || VALU kb2 elements 0-7 (finishing kb1 8-15)
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      grad_gap(g, 1, Y);
+      valu_gap(g, X, 0, Y, 1);
+      if (g < 2) rc_load(NLs, nrc, 0, nr0, g + 2);
+      else if (g < 6) rc_load(NDs, nrc, 1, nr0, g - 2);
+      else da[g - 4] = qrow(nslot + HS_TILE_B, nr0, g - 4);
+      sgap(5, g);
+    }
+  };
+
+  // staging by LDS-DMA straight into the ring (the arch half has no room for staging registers): tile t+2's five
+  // pieces are issued at seg C gaps 1-7 of tile t's half 0. Its slot held tile t-2, which every wave finished reading
+  // before tile t-1's barrier. Tile t+1's barrier waits for all but the wave's five youngest operations (tile t+3's,
+  // issued in its half 0) and publishes tile t+2 for seg E of its half 1.
+  // prologue: tiles 0 and 1
+#pragma unroll
+  for (int i = 0; i < NOPS; ++i) dma_op(0, i);
+#pragma unroll
+  for (int i = 0; i < NOPS; ++i) dma_op(1, i);
+  hs_vmcnt<0>();
+  __syncthreads();
+  NLs = rcblk(rcs, 0, 0);
+  NDs = rcblk(rcs, 1, 0);
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qa[ks] = qrow(0, 0, ks);
+    da[ks] = qrow(HS_TILE_B, 0, ks);
+  }
+  // the prologue's reads complete here (as the narrow kernel)
+  __builtin_amdgcn_s_waitcnt(LGKM0_WAIT);
+  // one tile in ring slot SL (compile-time in the 4-tile unroll) or, SL < 0, t & 3 at run time
+  auto tile = [&](auto SL, int t) __attribute__((always_inline)) {
+    constexpr int SLC = decltype(SL)::value;
+    const int sl = SLC >= 0 ? SLC : t & (HS_NSLOT - 1);
+    const int nsl = SLC >= 0 ? (SLC + 1) & (HS_NSLOT - 1) : (t + 1) & (HS_NSLOT - 1);
+    const int slot = sl * HS_SLOT_B, nslot = nsl * HS_SLOT_B, nrc = nsl * RC_B;
+    // tile t+1 is published after seg A of half 1 (seg E of half 1 is its first reader): one barrier behind the
+    // counted wait for its pieces
+    auto stage = [&]() __attribute__((always_inline)) {
+      if (t + 1 < nqt) {
+        hs_vmcnt<NOPS>();
+        __builtin_amdgcn_s_barrier();
+      }
+    };
+    auto rstg0 = [&](int seg, int g) __attribute__((always_inline)) {
+      if (seg != 2 || !(g & 1)) return;
+      dma_op(t + 2, g >> 1);
+      if (g == 7) dma_op(t + 2, 4);
+    };
+    auto none = []() __attribute__((always_inline)) {};
+    auto nogap = [](int, int) __attribute__((always_inline)) {};
+    half(std::integral_constant<int, 0>{}, slot, 0, slot, sl * RC_B, 32, none, rstg0);   // segs E / F: rows 32-63
+    half(std::integral_constant<int, 1>{}, slot, 32, nslot, nrc, 0, stage, nogap);       // ... tile t+1's rows 0-31
+  };
+  int t = 0;
+  for (; t + 4 <= nqt; t += 4) {   // t & 3 == 0 here
+    tile(std::integral_constant<int, 0>{}, t);
+    tile(std::integral_constant<int, 1>{}, t + 1);
+    tile(std::integral_constant<int, 2>{}, t + 2);
+    tile(std::integral_constant<int, 3>{}, t + 3);
+  }
+  for (; t < nqt; ++t) tile(std::integral_constant<int, -1>{}, t);
+  hs_vmcnt<0>();   // the last tiles' staging loads (past the end: zeros) retire
+  // key block 2 of the last half (a half 1: set 1): elements 8-15 (finishing 0-7), then its dV / dK
+#pragma unroll
+  for (int g = 0; g < 8; ++g) valu_gap(g, 1, 1, 1, 0);
+  HS_MUL(P[1][14], S[1][14]);
+  HS_MUL(P[1][15], S[1][15]);
+  asm volatile("s_nop 0" ::: "memory");
+  HS_CVT(pk[1][1][3], S[1][14], S[1][15]);
+  HS_CVT(dd[1][1][2], P[1][12], P[1][13]);
+  HS_CVT(dd[1][1][3], P[1][14], P[1][15]);
+  asm volatile("s_nop 1" ::: "memory");
+#pragma unroll
+  for (int g = 0; g < 8; ++g) grad_gap(g, 2, 1);
+  // the accumulators are read by VALU next: let the last MFMAs retire (the compiler cannot see their latency)
+  asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+
+  // the lane's key and column are derived again from the thread index, made opaque: one register lives across the
+  // loop for the stores, not every value derived from it
+  int etid = tid;
+  HS_OPAQUE(etid);
+  const int eh = (etid >> 5) & 1, er32 = etid & 31;
+  const float sc = a.scale;
+#pragma unroll
+  for (int kb = 0; kb < 3; ++kb) {
+    const int key = kw0 + 32 * kb + er32;
+    if (key < L) {
+      bf16* dkp = a.dk + b * a.bs_dk + (long long)key * a.rs_dk + hh * a.hs;
+      bf16* dvp = a.dv + b * a.bs_dv + (long long)key * a.rs_dv + hh * a.hs;
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          bf16x4 k4, v4;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            k4[j] = to_bf16(dk[db][kb][4 * g + j] * sc);
+            v4[j] = to_bf16(dv[db][kb][4 * g + j]);
+          }
+          *(bf16x4*)(dkp + 32 * db + 8 * g + 4 * eh) = k4;
+          *(bf16x4*)(dvp + 32 * db + 8 * g + 4 * eh) = v4;
         }
     }
   }
@@ -2549,13 +2903,44 @@ extern "C" long long lci_attn_bwd_ws_bytes(int B, int H, int L) {
   return ((dq4_flag_offset(B, H, L) + flags) * 4 + 255) / 256 * 256;
 }
 
+// How lci_attn_bwd splits the keys of the dK/dV pass: the number W of attn_bwd_dkdv_hs3_kernel workgroups (384 keys
+// each, keys [0, 384 W)) per (batch, head); attn_bwd_dkdv_hs_kernel takes the keys from 384 W on. 0 = the narrow
+// kernel alone. A split qualifies when both grids pass attn_wide_pick's rule (at least n_cu workgroups and >= 0.9 of
+// the rounds they occupy; the narrow grid may also be empty). A wide workgroup does 1.5 narrow workgroups' work, so
+// a split costs 3 rounds_wide + 2 rounds_narrow against 2 rounds of the narrow kernel alone: the cheapest qualifying
+// split is taken (the larger W on a tie) if it costs no more than the narrow kernel alone. Pure host arithmetic.
+// The metric shape (B H = 12, L = 65536, 256 CUs): W = 128, 6 wide + 3 narrow rounds; L = 16384 and 32768: 0.
+// (DESIGN.md "Attention backward dK/dV: 96 keys per wave on a split key grid" has the measurements.)
+static bool attn_grid_fills(long long wgs, int n_cu) {
+  return wgs >= n_cu && 10 * wgs >= 9 * ((wgs + n_cu - 1) / n_cu) * n_cu;
+}
+extern "C" int lci_attn_bwd_dkdv_pick(int B, int L, int H, int n_cu) {
+  if (B <= 0 || L <= 0 || H <= 0 || n_cu <= 0) return 0;
+  const long long bh = (long long)B * H;
+  const int nkw = HS_NW * 64;
+  long long best_cost = 2 * ((bh * ((L + nkw - 1) / nkw) + n_cu - 1) / n_cu);
+  int best = 0;
+  for (int W = 1; W <= L / DKV3_KWG; ++W) {
+    const long long wide = bh * W, rest = bh * ((L - DKV3_KWG * W + nkw - 1) / nkw);
+    if (!attn_grid_fills(wide, n_cu) || (rest && !attn_grid_fills(rest, n_cu))) continue;
+    const long long cost = 3 * ((wide + n_cu - 1) / n_cu) + 2 * ((rest + n_cu - 1) / n_cu);
+    if (cost <= best_cost) best_cost = cost, best = W;
+  }
+  return best;
+}
+
 // dq_variant: -1 = lci_attn_bwd_dq_pick, 0 = attn_bwd_dq_hs_kernel, 1 = attn_bwd_dq_hs4_kernel + its fallback launch;
+// dkdv_wide_wgs: -1 = lci_attn_bwd_dkdv_pick, 0 = attn_bwd_dkdv_hs_kernel alone, W > 0 = attn_bwd_dkdv_hs3_kernel on
+// keys [0, 384 W) (384 (W - 1) < L) and the narrow kernel on the rest;
 // stage: -1 = all launches; 0 = delta, 1 = dK/dV, 2 = dQ (for per-kernel timing)
-extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, const void* out, const void* dout,
-                                    const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H, int head_dim,
-                                    float scale, void* stream) {
+extern "C" int lci_attn_bwd_variant2(int dq_variant, int dkdv_wide_wgs, int stage, const void* qkv, const void* out,
+                                     const void* dout, const float* lse2, void* dqkv, float* delta_ws, int B, int L,
+                                     int H, int head_dim, float scale, void* stream) {
   LCI_CHECK(dq_variant >= -1 && dq_variant <= 1, "lci_attn_bwd_variant: dq_variant %d (want -1, 0 or 1)", dq_variant);
   if (attn_check("lci_attn_bwd", qkv, dqkv, out, dout, B, L, H, head_dim)) return 1;
+  LCI_CHECK(dkdv_wide_wgs >= -1 && (dkdv_wide_wgs <= 0 || (long long)DKV3_KWG * (dkdv_wide_wgs - 1) < L),
+            "lci_attn_bwd_variant2: dkdv_wide_wgs %d (want -1, 0 or at most ceil(L / 384) = %d)", dkdv_wide_wgs,
+            (L + DKV3_KWG - 1) / DKV3_KWG);
   LCI_CHECK(delta_ws != nullptr, "lci_attn_bwd: delta_ws (lci_attn_bwd_ws_bytes) is required");
   AttnArgs a = attn_args(qkv, L, H, scale);
   bf16* dbase = (bf16*)dqkv;
@@ -2573,8 +2958,17 @@ extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, 
     LCI_LAUNCH_CHECK();
   }
   if (stage < 0 || stage == 1) {
-    hipLaunchKernelGGL(attn_bwd_dkdv_hs_kernel, grid, dim3(HS_NW * 64), 0, s, a);
-    LCI_LAUNCH_CHECK();
+    const int W = dkdv_wide_wgs < 0 ? lci_attn_bwd_dkdv_pick(B, L, H, attn_n_cu()) : dkdv_wide_wgs;
+    if (W > 0) {
+      hipLaunchKernelGGL(attn_bwd_dkdv_hs3_kernel, dim3(W, H, B), dim3(HS_NW * 64), 0, s, a);
+      LCI_LAUNCH_CHECK();
+    }
+    a.k0 = W * DKV3_KWG;   // the narrow kernel's first key
+    if (a.k0 < L) {
+      hipLaunchKernelGGL(attn_bwd_dkdv_hs_kernel, dim3((L - a.k0 + HS_NW * 64 - 1) / (HS_NW * 64), H, B),
+                         dim3(HS_NW * 64), 0, s, a);
+      LCI_LAUNCH_CHECK();
+    }
   }
   if (stage < 0 || stage == 2) {
     if (dq_variant < 0) dq_variant = lci_attn_bwd_dq_pick(B, L, H, attn_n_cu());
@@ -2589,6 +2983,13 @@ extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, 
     LCI_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int lci_attn_bwd_variant(int dq_variant, int stage, const void* qkv, const void* out, const void* dout,
+                                    const float* lse2, void* dqkv, float* delta_ws, int B, int L, int H, int head_dim,
+                                    float scale, void* stream) {
+  return lci_attn_bwd_variant2(dq_variant, -1, stage, qkv, out, dout, lse2, dqkv, delta_ws, B, L, H, head_dim, scale,
+                               stream);
 }
 
 extern "C" int lci_attn_bwd_stage(int stage, const void* qkv, const void* out, const void* dout, const float* lse2,

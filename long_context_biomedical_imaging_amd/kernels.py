@@ -126,6 +126,16 @@ def attn_bwd_variant(qkv, out, dout, lse2, num_heads: int, scale: float, dq_vari
     return dqkv, ws[n0:n0 + B * num_heads * nwg].view(B, num_heads, nwg)
 
 
+def attn_bwd_variant2(qkv, out, dout, lse2, num_heads: int, scale: float, dq_variant: int, dkdv_wide_wgs: int,
+                      stage: int = -1, ws=None, dqkv=None):
+    """attn_bwd_variant with the dK/dV key split forced as well (include/lci.h lci_attn_bwd_variant2: W > 0 = the
+    96-keys-per-wave kernel on keys [0, 384 W) and the 64-key kernel on the rest, 0 = the 64-key kernel alone, -1 = the
+    library's pick). Returns dqkv."""
+    _, _, _, dqkv, _, args = _attn_bwd_setup(qkv, out, dout, lse2, num_heads, scale, dqkv, ws)
+    _lib.call("lci_attn_bwd_variant2", int(dq_variant), int(dkdv_wide_wgs), int(stage), *args)
+    return dqkv
+
+
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, num_heads, scale):
