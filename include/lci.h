@@ -79,13 +79,24 @@ extern "C" {
  * 35: lci_attn_fwd_variant, lci_attn_fwd_pick; 36: lci_attn_bwd_variant, lci_attn_bwd_dq_pick, lci_attn_bwd_ws_bytes
  * grows by the wide dQ kernel's per-workgroup flags; 37: lci_enhance_metrics, lci_seg_f1 (+ _ws_bytes), lci_ssim_tile;
  * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef; 39: lci_class_*;
- * 40: lci_augment (+ _ws_bytes); 41: lci_attn_bwd_variant2, lci_attn_bwd_dkdv_pick. */
-#define LCI_ABI_VERSION 41
+ * 40: lci_augment (+ _ws_bytes); 41: lci_attn_bwd_variant2, lci_attn_bwd_dkdv_pick; 42: the deterministic mode:
+ * lci_ordered_sum, lci_selective_scan_bwd_det, lci_hyena_pre_bwd_det, lci_fftconv_bwd_det, lci_patch_embed_bwd_det
+ * (+ _ws_bytes each). */
+#define LCI_ABI_VERSION 42
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
  * library whose hash differs from the sources beside it. */
 const char* lci_build_hash(void);
+
+/* ------------------------------------------------------------------ deterministic mode: the ordered sum
+ * The *_det entry points below return every gradient as a fixed-order sum with no float atomic on its path: each
+ * contributor stores its partial once with plain stores into a caller-owned workspace and this launch adds them,
+ *     out[c] = sum over r < rows of part[r * row_stride + c * col_stride],   c < n,
+ * one writer per out[c], in an order of additions fixed by `rows` alone (csrc/ordered_sum.hip). Same inputs, same
+ * shapes, same build: same bits. Every output of a *_det entry point is written; none needs a zero fill. */
+int lci_ordered_sum(const float* part, long long row_stride, int col_stride, int rows, long long n, float* out,
+                    void* stream);
 
 /* ------------------------------------------------------------------ ViT full self-attention (flash)
  * qkv : (B, L, 3*H*64) bf16, the packed qkv Linear output, channel order (qkv, head, d)
@@ -289,6 +300,17 @@ int lci_selective_scan_bwd(int dtype, const void* u, const void* delta, const fl
                            const long long* strides, int B, int L, int Dx, int N, int chunk, int delta_softplus,
                            const float* sdt, const void* ckpt, float* gl, float* gin, void* stream);
 int lci_selective_scan_bwd_plain_dbc(int L, int Dx, int chunk);
+/* Deterministic mode: lci_selective_scan_bwd with dBC, dA, dD, ddelta_bias written (dD / ddelta_bias may be null).
+ * The waves of a workgroup add their per-token dB / dC sums in wave order; where the channels span several
+ * workgroups each writes a (B, L, 16) slab of ws (lci_selective_scan_bwd_det_ws_bytes bytes, 0 when one workgroup
+ * holds every channel: ws may then be null) and the slabs are summed in order; dA / dD / ddelta_bias are ordered
+ * sums of per-(b, chunk) partials left in gin / gl at every chunk length. */
+long long lci_selective_scan_bwd_det_ws_bytes(int B, int L, int Dx, int chunk);
+int lci_selective_scan_bwd_det(int dtype, const void* u, const void* delta, const float* A, const void* Bm,
+                               const void* Cm, const float* D, const float* delta_bias, const void* dy, void* du,
+                               void* ddelta, float* dBC, float* dA, float* dD, float* ddelta_bias,
+                               const long long* strides, int B, int L, int Dx, int N, int chunk, int delta_softplus,
+                               const float* sdt, const void* ckpt, float* gl, float* gin, float* ws, void* stream);
 
 /* SiLU(depthwise conv1d(k = 3, 'same')) of both channel halves of in (B, L, 2C) (token stride in_ts):
  * ox (B, L, C) (token stride ox_ts) and oz at column offset zoff of a (B, L, oz_ts) buffer. */
@@ -342,6 +364,13 @@ int lci_fftconv_fwd(const float* u, const void* K, const float* Dv, float* y, vo
 int lci_fftconv_bwd(const float* dy, const float* u, const void* K, const float* Dv, float* du, float* dk,
                     float* dD, void* S, void* S2, const void* Su, void* SK, const void* tw, int R, int C, int L,
                     void* stream);
+/* Deterministic mode: lci_fftconv_bwd with dD written: dk[:, 0] with dk, else per-(row, 16384-element split) dot
+ * products stored to dd_ws (lci_fftconv_bwd_det_ws_bytes bytes; may be null with dk or without dD) and summed in
+ * order. */
+long long lci_fftconv_bwd_det_ws_bytes(int R, int C, int L);
+int lci_fftconv_bwd_det(const float* dy, const float* u, const void* K, const float* Dv, float* du, float* dk,
+                        float* dD, void* S, void* S2, const void* Su, void* SK, const void* tw, float* dd_ws, int R,
+                        int C, int L, void* stream);
 /* Direct causal long convolution for short rows (L <= lci_direct_conv_max_len(): the Swin-window sequences of
  * backbone_swin.py:361-362), exact f32 products on the f32 MFMA instead of an FFT. u, y (R, C, L) f32 channel-major
  * rows (filter of row r*C + c is c), k (C, L), D (C) f32 or null.
@@ -371,6 +400,13 @@ int lci_hyena_post_bwd(int dtype, const float* y, const void* x2, const void* do
 int lci_hyena_pre_bwd(int dtype, const void* z, const float* w, const float* bias, const float* dvg,
                       const void* gx2, void* dz, float* dw, float* db, int BB, int L, int H, int hd, int K,
                       void* stream);
+
+/* Deterministic mode: lci_hyena_pre_bwd with dw, db written: every workgroup stores its (3D, K + 1) sums to a row of
+ * ws (lci_hyena_pre_bwd_det_ws_bytes bytes) and the rows are summed in order. */
+long long lci_hyena_pre_bwd_det_ws_bytes(int BB, int L, int H, int hd, int K);
+int lci_hyena_pre_bwd_det(int dtype, const void* z, const float* w, const float* bias, const float* dvg,
+                          const void* gx2, void* dz, float* dw, float* db, float* ws, int BB, int L, int H, int hd,
+                          int K, void* stream);
 
 /* ------------------------------------------------------------------ Hyena implicit filter (order = D = 64)
  * prep: the f32 parameters W1 (64, E), b1, freq (64), W2, b2, W3, b3 (64x64, 64), W4 (64, 64), deltas (64) ->
@@ -431,6 +467,13 @@ int lci_patch_embed_fwd(const void* x, int x_dtype, const float* w, const float*
 int lci_patch_embed_bwd(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dw, float* db, float* dpos,
                         int B, int C, int D, int nd, const int* img_size, const int* patch, int channels_last,
                         void* stream);
+/* Deterministic mode: dw, db, dpos written. A sample's token tiles are strided over at most max(1, 1024 / B)
+ * workgroups, each keeping its (D, K + 1) sums in a row of ws (lci_patch_embed_bwd_det_ws_bytes bytes, -1 on a bad
+ * shape); the rows are summed in order. */
+long long lci_patch_embed_bwd_det_ws_bytes(int B, int C, int D, int nd, const int* img_size, const int* patch);
+int lci_patch_embed_bwd_det(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dw, float* db,
+                            float* dpos, float* ws, int B, int C, int D, int nd, const int* img_size,
+                            const int* patch, int channels_last, void* stream);
 
 /* ------------------------------------------------------------------ transformer-block LayerNorm
  * x (rows, C) f32 residual stream, C % 4 == 0, C <= 2048; gamma, beta (C) f32; eps as nn.LayerNorm's.

@@ -67,6 +67,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--gaussian_blur_aug", type=str_to_bool, default=True)
     p.add_argument("--use_amp", action="store_true")
     p.add_argument("--ddp", action="store_true")
+    # not a reference flag: bitwise-reproducible gradients (kernels.deterministic_mode for every training step)
+    p.add_argument("--deterministic", action="store_true")
     p.add_argument("--optim_type", type=str, default="adam", choices=["adam", "adamw", "sgd", "nadam"])
     p.add_argument("--optim.lr", type=float, default=1e-4)
     p.add_argument("--optim.weight_decay", type=float, default=0.0)

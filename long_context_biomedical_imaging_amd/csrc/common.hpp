@@ -110,6 +110,10 @@ __device__ __forceinline__ float wave_sum_xor32(float v) {
 // ------------------------------------------------------------------ host-side error plumbing
 namespace lci {
 void set_error(const char* fmt, ...);
+// out[c] = sum_r part[r * row_stride + c * col_stride] (c < n, r < rows) in an order fixed by `rows` alone: the sum
+// pass of the deterministic mode's store-and-sum form (ordered_sum.hip). Returns nonzero after set_error.
+int ordered_sum(const float* part, long long row_stride, int col_stride, int rows, long long n, float* out,
+                hipStream_t s);
 }
 
 #define LCI_CHECK(cond, ...)           \

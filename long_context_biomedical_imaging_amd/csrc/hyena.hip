@@ -994,7 +994,10 @@ __global__ __launch_bounds__(256) void dd_from_dk_kernel(const float* dk, float*
 
 // dD[j] += sum_rows sum_t a[row][t] * b[row][t] over rows of filter j (block partial + one atomic per block).
 // grid (rows, splits): a block takes a contiguous span of its row; 16-byte loads when the rows allow them.
+// DET (the deterministic mode): the block's sum is stored to out[(r_outer * splits + split) * C + j] instead, one
+// partial per (row, split), for lci::ordered_sum over the r_outer * splits rows.
 constexpr int RD_SPAN = 16384;   // elements per block
+template <bool DET = false>
 __global__ __launch_bounds__(256) void row_dot_kernel(const float* x, const float* y, float* out, int L, int C,
                                                       int vec) {
   __shared__ float red[4];
@@ -1025,7 +1028,12 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float* x, const floa
   for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(out + j, (red[0] + red[1]) + (red[2] + red[3]));
+  if constexpr (DET) {
+    if (threadIdx.x == 0)
+      out[((long long)(row / C) * gridDim.y + blockIdx.y) * C + j] = (red[0] + red[1]) + (red[2] + red[3]);
+  } else {
+    if (threadIdx.x == 0) atomicAdd(out + j, (red[0] + red[1]) + (red[2] + red[3]));
+  }
 }
 
 __global__ void twiddle_kernel(f32x2* tw, int n) {
@@ -1185,7 +1193,10 @@ __global__ __launch_bounds__(256) void hyena_pre_fwd2_kernel(GateArgs a) {
 // dw[c][i] += sum_s dconv_c[s] z[s + i - (K - 1)][c]; db[c] += sum_s dconv_c[s]. Workgroups stride over token
 // tiles (so the dw/db partials are reduced over the waves and tiles in registers / LDS first and each workgroup
 // adds them once: a few hundred float atomics per address instead of one per 64-token run).
-template <typename T, int KC>
+// DET (the deterministic mode): a.dw / a.db point into a partial buffer of rows [dw (3D, K) | db (3D)], one row per
+// (bb, blockIdx.x); each workgroup stores its sums to its row (the workgroups of one row hold disjoint channels)
+// and lci::ordered_sum adds the rows.
+template <typename T, int KC, bool DET = false>
 __global__ __launch_bounds__(256) void hyena_pre_bwd2_kernel(GateArgs a) {
   constexpr int W = HY_TT + KC - 1;            // dvg tile width: the tile's tokens + the K - 1 lookahead
   constexpr int NR = 2 * KC - 1;               // z ring: taps of the conv at tn and of dw at s = tn - K + 1
@@ -1290,6 +1301,12 @@ __global__ __launch_bounds__(256) void hyena_pre_bwd2_kernel(GateArgs a) {
     const int hh = c / a.hd, jc = c - hh * a.hd;
     const int grp = i / (KC + 1), k = i - grp * (KC + 1);
     const int cc = hh * 3 * a.hd + grp * a.hd + jc;
+    if constexpr (DET) {
+      const long long ro = ((long long)bb * gridDim.x + blockIdx.x) * (3 * a.D * (KC + 1));
+      if (k < KC) a.dw[ro + cc * KC + k] = sum;
+      else if (a.db) a.db[ro + cc] = sum;
+      continue;
+    }
     if (k < KC) atomicAdd(a.dw + cc * KC + k, sum);
     else if (a.db) atomicAdd(a.db + cc, sum);
   }
@@ -1450,7 +1467,8 @@ __global__ __launch_bounds__(256) void hyena_pre_fwd3_kernel(GateArgs a) {
 }
 
 // dz / dw / db of the short conv + gates (see hyena_pre_bwd2_kernel), token tiles strided over a persistent grid.
-template <int KC>
+// DET: as in hyena_pre_bwd2_kernel.
+template <int KC, bool DET = false>
 __global__ __launch_bounds__(256) void hyena_pre_bwd3_kernel(GateArgs a) {
   constexpr int ZR = HG_TT + 2 * KC - 2;        // z rows: tokens t0 - KC + 1 .. t0 + TT + KC - 2
   constexpr int W = HG_TT + KC - 1;             // dconv tokens t0 .. t0 + TT + KC - 2
@@ -1569,6 +1587,12 @@ __global__ __launch_bounds__(256) void hyena_pre_bwd3_kernel(GateArgs a) {
     const float sum = (red[i * 64 + l] + red[(NA + i) * 64 + l]) + (red[(2 * NA + i) * 64 + l] + red[(3 * NA + i) * 64 + l]);
     const int grp = i / (KC + 1), k = i - grp * (KC + 1);
     const int cc = hg_zcol(c, grp, a.hd);
+    if constexpr (DET) {
+      const long long ro = ((long long)bb * gridDim.x + blockIdx.x) * (3 * D * (KC + 1));
+      if (k < KC) a.dw[ro + cc * KC + k] = sum;
+      else if (a.db) a.db[ro + cc] = sum;
+      continue;
+    }
     if (k < KC) atomicAdd(a.dw + cc * KC + k, sum);
     else if (a.db) atomicAdd(a.db + cc, sum);
   }
@@ -1732,8 +1756,8 @@ extern "C" int lci_fftconv_bwd(const float* dy, const float* u, const void* K, c
     LCI_LAUNCH_CHECK();
   } else if (dD) {
     const int vec = (L % 4 == 0) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)u & 15) == 0;
-    hipLaunchKernelGGL(row_dot_kernel, dim3(R * C, (L + RD_SPAN - 1) / RD_SPAN), dim3(256), 0, s, dy, u, dD, L, C,
-                       vec);
+    hipLaunchKernelGGL(row_dot_kernel<false>, dim3(R * C, (L + RD_SPAN - 1) / RD_SPAN), dim3(256), 0, s, dy, u, dD,
+                       L, C, vec);
     LCI_LAUNCH_CHECK();
   }
   return 0;
@@ -1806,20 +1830,22 @@ extern "C" int lci_hyena_post_bwd(int dtype, const float* y, const void* x2, con
   return 0;
 }
 
-// dw (3D, K), db (3D) accumulated (caller zeroes). gx2 (BB, L, D) in z's dtype.
-extern "C" int lci_hyena_pre_bwd(int dtype, const void* z, const float* w, const float* bias, const float* dvg,
-                                 const void* gx2, void* dz, float* dw, float* db, int BB, int L, int H, int hd, int K,
-                                 void* stream) {
-  LCI_CHECK(K >= 1 && K <= 8, "hyena_pre: short filter order %d unsupported (<= 8)", K);
-  GateArgs a{};
-  a.z = z; a.w = w; a.bias = bias; a.dvg = dvg; a.gx2 = gx2; a.dz = dz; a.dw = dw; a.db = db;
-  a.BB = BB; a.L = L; a.H = H; a.hd = hd; a.D = H * hd; a.K = K;
-  if (hg_v3_ok(a, dtype, {z, dvg, gx2, dz})) {   // persistent: ~2 workgroups per CU stride over the token tiles
+// The launches of lci_hyena_pre_bwd (DET = false) and lci_hyena_pre_bwd_det: *rows receives gridDim.x * BB, the number
+// of partial rows the DET kernels write.
+static int hyena_pre_gx(int ntiles, int ncy, int BB, int budget) {
+  return std::max(1, std::min(ntiles, budget / std::max(1, ncy * BB)));
+}
+
+template <bool DET>
+static int hyena_pre_bwd_launch(const GateArgs& a, int dtype, int* rows, void* stream) {
+  const int BB = a.BB, L = a.L, K = a.K;
+  if (hg_v3_ok(a, dtype, {a.z, a.dvg, a.gx2, a.dz})) {   // persistent: ~2 workgroups per CU stride over the token tiles
     const int ntiles = (L + HG_TT - 1) / HG_TT, ncy = (a.D + 63) / 64;
-    const int gx = std::max(1, std::min(ntiles, 512 / std::max(1, ncy * BB)));
+    const int gx = hyena_pre_gx(ntiles, ncy, BB, 512);
+    *rows = gx * BB;
     dim3 grid3(gx, ncy, BB);
 #define LCI_PRE_BWD3(KK) \
-  case KK: hipLaunchKernelGGL(hyena_pre_bwd3_kernel<KK>, grid3, dim3(256), 0, (hipStream_t)stream, a); LCI_LAUNCH_CHECK(); return 0;
+  case KK: hipLaunchKernelGGL((hyena_pre_bwd3_kernel<KK, DET>), grid3, dim3(256), 0, (hipStream_t)stream, a); LCI_LAUNCH_CHECK(); return 0;
     switch (K) {
       LCI_PRE_BWD3(1) LCI_PRE_BWD3(2) LCI_PRE_BWD3(3) LCI_PRE_BWD3(4) LCI_PRE_BWD3(5) LCI_PRE_BWD3(6) LCI_PRE_BWD3(7)
       LCI_PRE_BWD3(8)
@@ -1829,14 +1855,15 @@ extern "C" int lci_hyena_pre_bwd(int dtype, const void* z, const float* w, const
   }
   // one lane per output channel, token tiles strided over ~8 workgroups/CU (every order the C-ABI accepts)
   const int ntiles = (L + HY_TT - 1) / HY_TT, ncy = (a.D + 63) / 64;
-  const int gx = std::max(1, std::min(ntiles, 2048 / std::max(1, ncy * BB)));
+  const int gx = hyena_pre_gx(ntiles, ncy, BB, 2048);
+  *rows = gx * BB;
   dim3 grid2(gx, ncy, BB);
-#define LCI_PRE_BWD2(KK)                                                                                        \
-  case KK:                                                                                                    \
-    if (dtype == 1)                                                                                           \
-      hipLaunchKernelGGL((hyena_pre_bwd2_kernel<bf16, KK>), grid2, dim3(256), 0, (hipStream_t)stream, a);     \
-    else                                                                                                      \
-      hipLaunchKernelGGL((hyena_pre_bwd2_kernel<float, KK>), grid2, dim3(256), 0, (hipStream_t)stream, a);    \
+#define LCI_PRE_BWD2(KK)                                                                                           \
+  case KK:                                                                                                       \
+    if (dtype == 1)                                                                                              \
+      hipLaunchKernelGGL((hyena_pre_bwd2_kernel<bf16, KK, DET>), grid2, dim3(256), 0, (hipStream_t)stream, a);   \
+    else                                                                                                         \
+      hipLaunchKernelGGL((hyena_pre_bwd2_kernel<float, KK, DET>), grid2, dim3(256), 0, (hipStream_t)stream, a);  \
     break;
   switch (K) {
     LCI_PRE_BWD2(1) LCI_PRE_BWD2(2) LCI_PRE_BWD2(3) LCI_PRE_BWD2(4) LCI_PRE_BWD2(5) LCI_PRE_BWD2(6)
@@ -1846,4 +1873,64 @@ extern "C" int lci_hyena_pre_bwd(int dtype, const void* z, const float* w, const
 #undef LCI_PRE_BWD2
   LCI_LAUNCH_CHECK();
   return 0;
+}
+
+// dw (3D, K), db (3D) accumulated (caller zeroes). gx2 (BB, L, D) in z's dtype.
+extern "C" int lci_hyena_pre_bwd(int dtype, const void* z, const float* w, const float* bias, const float* dvg,
+                                 const void* gx2, void* dz, float* dw, float* db, int BB, int L, int H, int hd, int K,
+                                 void* stream) {
+  LCI_CHECK(K >= 1 && K <= 8, "hyena_pre: short filter order %d unsupported (<= 8)", K);
+  GateArgs a{};
+  a.z = z; a.w = w; a.bias = bias; a.dvg = dvg; a.gx2 = gx2; a.dz = dz; a.dw = dw; a.db = db;
+  a.BB = BB; a.L = L; a.H = H; a.hd = hd; a.D = H * hd; a.K = K;
+  int rows;
+  return hyena_pre_bwd_launch<false>(a, dtype, &rows, stream);
+}
+
+// Deterministic mode (lci.h). The workspace is sized for whichever dispatch branch has more partial rows, so the
+// size does not depend on pointer alignment.
+extern "C" long long lci_hyena_pre_bwd_det_ws_bytes(int BB, int L, int H, int hd, int K) {
+  const int D = H * hd, ncy = (D + 63) / 64;
+  const int gx = std::max(hyena_pre_gx((L + HG_TT - 1) / HG_TT, ncy, BB, 512),
+                          hyena_pre_gx((L + HY_TT - 1) / HY_TT, ncy, BB, 2048));
+  return (long long)gx * BB * 3 * D * (K + 1) * 4;
+}
+
+// dz, dw (3D, K) and db (3D, optional) are all written (no zero fill).
+extern "C" int lci_hyena_pre_bwd_det(int dtype, const void* z, const float* w, const float* bias, const float* dvg,
+                                     const void* gx2, void* dz, float* dw, float* db, float* ws, int BB, int L, int H,
+                                     int hd, int K, void* stream) {
+  LCI_CHECK(K >= 1 && K <= 8, "hyena_pre: short filter order %d unsupported (<= 8)", K);
+  LCI_CHECK(ws && dw, "hyena_pre_bwd_det: null dw or workspace");
+  GateArgs a{};
+  const long long nw = 3ll * H * hd * K, nb = 3ll * H * hd;
+  a.z = z; a.w = w; a.bias = bias; a.dvg = dvg; a.gx2 = gx2; a.dz = dz; a.dw = ws; a.db = db ? ws + nw : nullptr;
+  a.BB = BB; a.L = L; a.H = H; a.hd = hd; a.D = H * hd; a.K = K;
+  int rows = 0;
+  if (int rc = hyena_pre_bwd_launch<true>(a, dtype, &rows, stream)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (ordered_sum(ws, nw + nb, 1, rows, nw, dw, s)) return 3;
+  if (db && ordered_sum(ws + nw, nw + nb, 1, rows, nb, db, s)) return 3;
+  return 0;
+}
+
+// lci_fftconv_bwd with dD written (no zero fill) and no float atomic: with dk, dD = dk[:, 0] as there; without, the
+// row dot products as per-(row, split) partials in dd_ws (lci_fftconv_bwd_det_ws_bytes) and their ordered sum.
+extern "C" long long lci_fftconv_bwd_det_ws_bytes(int R, int C, int L) {
+  return (long long)R * ((L + RD_SPAN - 1) / RD_SPAN) * C * 4;
+}
+
+extern "C" int lci_fftconv_bwd_det(const float* dy, const float* u, const void* K, const float* Dv, float* du,
+                                   float* dk, float* dD, void* S, void* S2, const void* Su, void* SK, const void* tw,
+                                   float* dd_ws, int R, int C, int L, void* stream) {
+  if (int rc = lci_fftconv_bwd(dy, u, K, Dv, du, dk, nullptr, S, S2, Su, SK, tw, R, C, L, stream)) return rc;
+  if (!dD) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (dk) return ordered_sum(dk, 0, L, 1, C, dD, s) ? 3 : 0;
+  LCI_CHECK(dd_ws, "fftconv_bwd_det: dD without dk needs dd_ws");
+  const int vec = (L % 4 == 0) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)u & 15) == 0;
+  const int splits = (L + RD_SPAN - 1) / RD_SPAN;
+  hipLaunchKernelGGL(row_dot_kernel<true>, dim3(R * C, splits), dim3(256), 0, s, dy, u, dd_ws, L, C, vec);
+  LCI_LAUNCH_CHECK();
+  return ordered_sum(dd_ws, C, 1, R * splits, C, dD, s) ? 3 : 0;
 }

@@ -458,19 +458,26 @@ __device__ __forceinline__ float wave_reduce16p(const f32x2 (&vb)[4], const f32x
 // profiles/r05_scan_ab.txt).
 // PARTIALS: per-(b, chunk) dA / dD / d(delta_bias) partials into the lane's own gin entry (read at the start) and
 // its dead gl entry, summed by scan_param_reduce_kernel, instead of B * nch float atomics per address.
+// DET (the deterministic mode, lci_selective_scan_bwd_det; always with PARTIALS): no atomic anywhere. Every wave
+// stores its per-token dB/dC sums into a red slot of its own and flush adds the slots in wave order; the result
+// goes to a.dBC with plain stores, offset by one (B, L, 2N) slab per channel group (blockIdx.y) when the channels
+// span several workgroups, for the ordered sum over the slabs that follows.
 __device__ __forceinline__ f32x2 fma2(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 splat2(float v) { return f32x2{v, v}; }
 
-template <typename T, bool PARTIALS>
+template <typename T, bool PARTIALS, bool DET = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void scan_bwd_kernel(ScanArgs a) {
+  static_assert(PARTIALS || !DET, "the deterministic build writes parameter partials");
   constexpr int NP = SCAN_N / 2;   // state pairs
-  __shared__ float red[SB][2 * SCAN_N];
+  __shared__ float redw[DET ? 4 : 1][SB][2 * SCAN_N];   // DET: one slot per wave
+  float (&red)[SB][2 * SCAN_N] = redw[0];
   __shared__ __attribute__((aligned(16))) float bcs[SB][BCS];
   const ScanWave<1> w(a);
   const int tid = threadIdx.x, lane = w.lane, chunk = w.chunk, b = w.b, d = w.d, dd = w.dd, t0 = w.t0, t1 = w.t1;
   const bool valid = w.valid;
   const bool single = blockDim.x == 64;
-  for (int i = tid; i < SB * 2 * SCAN_N; i += blockDim.x) (&red[0][0])[i] = 0.f;
+  if constexpr (!DET)   // (DET: every wave stores each (t, j) of its slot before flush reads it)
+    for (int i = tid; i < SB * 2 * SCAN_N; i += blockDim.x) (&red[0][0])[i] = 0.f;
   f32x2 A2[NP], h[NP], dA[NP];
   {
     const float* gi = a.gin + w.sidx(a);
@@ -515,6 +522,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int i = k / (2 * SCAN_N), j = k % (2 * SCAN_N);
       const int t = blk0 + i;
       float* dst = a.dBC + ((long long)b * a.L + t) * (2 * SCAN_N) + j;
+      if constexpr (DET) {
+        if (t < t1) {
+          float v = redw[0][i][j];
+          for (int q = 1; q < (int)(blockDim.x >> 6); ++q) v += redw[q][i][j];
+          dst[(long long)blockIdx.y * a.B * a.L * (2 * SCAN_N)] = v;
+        }
+        continue;
+      }
       if (t < t1) {
         if (a.dbc_plain) *dst = red[i][j];
         else atomicAdd(dst, red[i][j]);
@@ -597,7 +612,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         ddcol.st(t, ddl);
         const float r = wave_reduce16p(vb, vc, lane);
         if ((lane & 3) == 0) {   // one wave per workgroup: the only writer of its (t, j) entry
-          if (single) red[t - blk0][lane >> 2] = r;
+          if constexpr (DET) redw[w.wv][t - blk0][lane >> 2] = r;
+          else if (single) red[t - blk0][lane >> 2] = r;
           else atomicAdd(&red[t - blk0][lane >> 2], r);
         }
       }
@@ -978,6 +994,62 @@ extern "C" int lci_selective_scan_bwd(int dtype, const void* u, const void* delt
     hipLaunchKernelGGL(scan_param_reduce_kernel, dim3((Dx * SCAN_NP + 255) / 256, ny), dim3(256), 0, s, a);
     LCI_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+// Deterministic mode (lci.h): the same passes with scan_bwd_kernel<T, true, true> at every chunk length and ordered
+// sums in place of every float atomic. ws: one (B, L, 2N) dBC slab per channel group when there is more than one.
+static int scan_bwd_groups(int Tc, int Dx) {
+  const int nwv = scan_bwd_waves(Tc, Dx);
+  return (Dx + nwv * 64 - 1) / (nwv * 64);
+}
+
+extern "C" long long lci_selective_scan_bwd_det_ws_bytes(int B, int L, int Dx, int chunk) {
+  const int ng = scan_bwd_groups(chunk, Dx);
+  return ng > 1 ? (long long)ng * B * L * 2 * SCAN_N * 4 : 0;
+}
+
+extern "C" int lci_selective_scan_bwd_det(int dtype, const void* u, const void* delta, const float* A, const void* Bm,
+                                          const void* Cm, const float* D, const float* delta_bias, const void* dy,
+                                          void* du, void* ddelta, float* dBC, float* dA, float* dD,
+                                          float* ddelta_bias, const long long* strides, int B, int L, int Dx, int N,
+                                          int chunk, int delta_softplus, const float* sdt, const void* ckpt, float* gl,
+                                          float* gin, float* ws, void* stream) {
+  ScanArgs a{};
+  if (scan_fill(a, B, L, Dx, N, chunk)) return 1;
+  a.softplus = delta_softplus;
+  if (scan_strides(a, strides, dtype)) return 1;
+  if (scan_check_bc(Bm, Cm, strides[5], strides[7], dtype)) return 1;
+  const int nwv = scan_bwd_waves(a.Tc, Dx), ng = scan_bwd_groups(a.Tc, Dx);
+  LCI_CHECK(ws || ng == 1, "selective_scan_bwd_det: ws is null with %d channel groups", ng);
+  LCI_CHECK(sdt || a.nch == 1, "selective_scan_bwd_det: sdt is null with %d chunks", a.nch);
+  a.u = u; a.delta = delta; a.A = A; a.Bm = Bm; a.Cm = Cm; a.D = D; a.dbias = delta_bias; a.dy = dy;
+  a.du = du; a.ddelta = ddelta; a.dBC = ng > 1 ? ws : dBC;
+  a.sdt = (float*)sdt; a.ckpt = const_cast<void*>(ckpt); a.gl = gl; a.gin = gin;
+  a.zero_carry = sdt == nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if (!a.zero_carry) {
+    dim3 grid((a.nch + 3) / 4, (Dx + 63) / 64, B);
+    with_dtype(dtype, [&](auto t) {
+      hipLaunchKernelGGL((scan_bwd_agg_kernel<typename decltype(t)::type>), grid, dim3(256), 0, s, a);
+    });
+    LCI_LAUNCH_CHECK();
+    hipLaunchKernelGGL(scan_carry_kernel<true>, dim3(Dx, B), dim3(64), 0, s, a);
+    LCI_LAUNCH_CHECK();
+  }
+  with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL((scan_bwd_kernel<typename decltype(t)::type, true, true>), dim3(a.nch, ng, B), dim3(nwv * 64),
+                       0, s, a);
+  });
+  LCI_LAUNCH_CHECK();
+  // the partials: dA in gin (rows, Dx, N), dD / d(delta_bias) in gl[..., 0] / gl[..., 1]
+  const int rows = B * a.nch;
+  const long long rs = (long long)Dx * SCAN_N;
+  if (ordered_sum(gin, rs, 1, rows, rs, dA, s)) return 3;
+  if (dD && ordered_sum(gl, rs, SCAN_N, rows, Dx, dD, s)) return 3;
+  if (ddelta_bias && ordered_sum(gl + 1, rs, SCAN_N, rows, Dx, ddelta_bias, s)) return 3;
+  const long long nbc = (long long)B * L * 2 * SCAN_N;
+  if (ng > 1 && ordered_sum(ws, nbc, 1, ng, nbc, dBC, s)) return 3;
   return 0;
 }
 

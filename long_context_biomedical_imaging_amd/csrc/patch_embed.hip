@@ -11,6 +11,8 @@
 // Backward: dpos[t, d] = sum_b dy[b, t, d] (direct), dbias/dW block-partial sums -> f32 atomics (D*K words).
 #include "common.hpp"
 
+#include <algorithm>
+
 namespace lci {
 
 struct PatchArgs {
@@ -122,6 +124,44 @@ __global__ __launch_bounds__(256) void patch_embed_bwd_w_kernel(PatchArgs a) {
   }
 }
 
+// The deterministic form of the kernel above: workgroup (blockIdx.x, b) strides over its sample's token tiles and
+// keeps its sums in row b * gridDim.x + blockIdx.x of part, laid out [dW (D, K) | db (D)] (db only when a.db), with
+// plain stores: the first tile stores, a later one adds to what the same thread stored. lci::ordered_sum then adds
+// the rows. a.dw = part.
+template <typename Tin, typename Tg>
+__global__ __launch_bounds__(256) void patch_embed_bwd_w_det_kernel(PatchArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sp[];  // [T][K]
+  const int b = blockIdx.y;
+  const Tin* x = (const Tin*)a.x;
+  const Tg* dy = (const Tg*)a.dy;
+  const int npairs = a.D * (a.K + 1);  // k == K column is the bias
+  float* row = a.dw + ((long long)b * gridDim.x + blockIdx.x) * npairs;
+  const int ntiles = (a.L + a.T - 1) / a.T;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int t0 = tile * a.T;
+    const int T = min(a.T, a.L - t0);
+    if (tile != (int)blockIdx.x) __syncthreads();   // the previous tile's reads of sp
+    for (int idx = threadIdx.x; idx < T * a.K; idx += blockDim.x) {
+      const int t = idx / a.K, k = idx % a.K;
+      sp[idx] = patch_val(a, x, b, t0 + t, k);
+    }
+    __syncthreads();
+    for (int pr = threadIdx.x; pr < npairs; pr += blockDim.x) {
+      const int d = pr / (a.K + 1), k = pr % (a.K + 1);
+      if (k == a.K && !a.db) continue;
+      float acc = 0.f;
+      for (int t = 0; t < T; ++t) {
+        const long long yi = a.channels_last ? ((long long)b * a.L + t0 + t) * a.D + d
+                                             : ((long long)b * a.D + d) * a.L + t0 + t;
+        const float g = (float)dy[yi];
+        acc = fmaf(g, k < a.K ? sp[t * a.K + k] : 1.f, acc);
+      }
+      float* dst = row + (k < a.K ? d * a.K + k : a.D * a.K + d);
+      *dst = tile == (int)blockIdx.x ? acc : *dst + acc;
+    }
+  }
+}
+
 // dpos[t, d] = sum_b dy[b, t, d]   (channels-last only)
 template <typename Tg>
 __global__ __launch_bounds__(256) void patch_embed_bwd_pos_kernel(PatchArgs a) {
@@ -147,6 +187,15 @@ static int fill_args(PatchArgs& a, int B, int C, int D, int nd, const int* S, co
   LCI_CHECK(a.K <= 4096, "patch_embed: patch volume %d too large", a.K);
   a.T = 4096 / a.K; if (a.T > 64) a.T = 64;
   LCI_CHECK(!channels_last || D % 4 == 0, "patch_embed: D %% 4 != 0");
+  return 0;
+}
+
+static int launch_dpos(const PatchArgs& a, int dy_dtype, hipStream_t s) {
+  const long long n = (long long)a.L * a.D;
+  int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096;
+  if (dy_dtype == 0) hipLaunchKernelGGL((patch_embed_bwd_pos_kernel<float>), dim3(blocks), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((patch_embed_bwd_pos_kernel<bf16>), dim3(blocks), dim3(256), 0, s, a);
+  LCI_LAUNCH_CHECK();
   return 0;
 }
 
@@ -193,12 +242,47 @@ extern "C" int lci_patch_embed_bwd(const void* x, int x_dtype, const void* dy, i
   else if (x_dtype == 1 && dy_dtype == 1) hipLaunchKernelGGL((patch_embed_bwd_w_kernel<bf16, bf16>), grid, dim3(256), sh, s, a);
   else LCI_CHECK(false, "patch_embed_bwd: dtype codes %d/%d", x_dtype, dy_dtype);
   LCI_LAUNCH_CHECK();
-  if (dpos) {
-    const long long n = (long long)a.L * D;
-    int blocks = (int)((n + 255) / 256); if (blocks > 4096) blocks = 4096;
-    if (dy_dtype == 0) hipLaunchKernelGGL((patch_embed_bwd_pos_kernel<float>), dim3(blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((patch_embed_bwd_pos_kernel<bf16>), dim3(blocks), dim3(256), 0, s, a);
-    LCI_LAUNCH_CHECK();
-  }
-  return 0;
+  return dpos ? launch_dpos(a, dy_dtype, s) : 0;
+}
+
+// Deterministic mode (lci.h): per-workgroup partial rows + the ordered sum. A sample's token tiles are strided over
+// at most max(1, 1024 / B) workgroups, which bounds the partial buffer at about 1024 rows whatever the volume.
+static int patch_det_groups(int B, int ntiles) { return std::max(1, std::min(ntiles, 1024 / std::max(1, B))); }
+
+static void patch_bwd_tile(PatchArgs& a) {   // tokens per tile of the weight-gradient kernels, bounded by LDS
+  a.T = 16384 / a.K; if (a.T > 256) a.T = 256; if (a.T < 1) a.T = 1;
+}
+
+extern "C" long long lci_patch_embed_bwd_det_ws_bytes(int B, int C, int D, int nd, const int* img_size,
+                                                      const int* patch) {
+  PatchArgs a{};
+  if (fill_args(a, B, C, D, nd, img_size, patch, 0)) return -1;
+  patch_bwd_tile(a);
+  return (long long)B * patch_det_groups(B, (a.L + a.T - 1) / a.T) * D * (a.K + 1) * 4;
+}
+
+// dw (D*K), db (D) and dpos (L, D) are all written (no zero fill); ws: lci_patch_embed_bwd_det_ws_bytes bytes.
+extern "C" int lci_patch_embed_bwd_det(const void* x, int x_dtype, const void* dy, int dy_dtype, float* dw, float* db,
+                                       float* dpos, float* ws, int B, int C, int D, int nd, const int* img_size,
+                                       const int* patch, int channels_last, void* stream) {
+  PatchArgs a{};
+  if (fill_args(a, B, C, D, nd, img_size, patch, channels_last)) return 1;
+  LCI_CHECK(!(dpos && !channels_last), "patch_embed: dpos only with channels-last tokens");
+  LCI_CHECK(ws && dw, "patch_embed_bwd_det: null dw or workspace");
+  a.x = x; a.dy = dy; a.dw = ws; a.db = db; a.dpos = dpos;
+  hipStream_t s = (hipStream_t)stream;
+  patch_bwd_tile(a);
+  const int gx = patch_det_groups(B, (a.L + a.T - 1) / a.T);
+  dim3 grid(gx, B);
+  const size_t sh = (size_t)a.T * a.K * 4;
+  if (x_dtype == 0 && dy_dtype == 0) hipLaunchKernelGGL((patch_embed_bwd_w_det_kernel<float, float>), grid, dim3(256), sh, s, a);
+  else if (x_dtype == 0 && dy_dtype == 1) hipLaunchKernelGGL((patch_embed_bwd_w_det_kernel<float, bf16>), grid, dim3(256), sh, s, a);
+  else if (x_dtype == 1 && dy_dtype == 0) hipLaunchKernelGGL((patch_embed_bwd_w_det_kernel<bf16, float>), grid, dim3(256), sh, s, a);
+  else if (x_dtype == 1 && dy_dtype == 1) hipLaunchKernelGGL((patch_embed_bwd_w_det_kernel<bf16, bf16>), grid, dim3(256), sh, s, a);
+  else LCI_CHECK(false, "patch_embed_bwd_det: dtype codes %d/%d", x_dtype, dy_dtype);
+  LCI_LAUNCH_CHECK();
+  const long long rs = (long long)D * (a.K + 1), nw = (long long)D * a.K;
+  if (ordered_sum(ws, rs, 1, gx * B, nw, dw, s)) return 3;
+  if (db && ordered_sum(ws + nw, rs, 1, gx * B, D, db, s)) return 3;
+  return dpos ? launch_dpos(a, dy_dtype, s) : 0;
 }

@@ -1,6 +1,7 @@
 """torch.autograd wrappers over the liblci C-ABI. Each op runs the HIP kernels; none has a CPU path."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -50,6 +51,37 @@ class KernelTimer:
     @classmethod
     def reset(cls):
         cls.records = []
+
+
+# ------------------------------------------------------------------------------ deterministic mode
+_DET_OVERRIDE = False
+
+
+def deterministic() -> bool:
+    """Whether the ops return bitwise-reproducible gradients (the *_det entry points: fixed-order sums, no float
+    atomic). Read at call time: an override set by deterministic_mode(), LCI_DETERMINISTIC=1 in the environment, or
+    torch.use_deterministic_algorithms(True). Each autograd Function reads it once in forward and keeps it in ctx,
+    so a backward follows the mode its forward saw."""
+    return (_DET_OVERRIDE or os.environ.get("LCI_DETERMINISTIC", "0") == "1"
+            or torch.are_deterministic_algorithms_enabled())
+
+
+@contextlib.contextmanager
+def deterministic_mode(flag: bool = True):
+    """Set the deterministic-mode override inside the block (flag=False sets none: the environment variable and
+    torch's switch still count) and restore the previous one on exit."""
+    global _DET_OVERRIDE
+    prev = _DET_OVERRIDE
+    _DET_OVERRIDE = bool(flag)
+    try:
+        yield
+    finally:
+        _DET_OVERRIDE = prev
+
+
+def _ws(nbytes: int, device):
+    """A partial-sum workspace of at least `nbytes` bytes (f32), allocated by torch: safe under graph capture."""
+    return torch.empty(max(1, -(-int(nbytes) // 4)), device=device, dtype=torch.float32)
 
 
 # ------------------------------------------------------------------------------------- attention
@@ -267,6 +299,7 @@ class _PatchEmbed(torch.autograd.Function):
                   y.data_ptr(), _lib.DTYPE[out_dtype], B, C, D, len(S), _lib.c_array(ctypes.c_int, S, 3, 1),
                   _lib.c_array(ctypes.c_int, P, 3, 1), int(channels_last), _lib.stream_of(x))
         ctx.save_for_backward(x)
+        ctx.det = deterministic()
         ctx.meta = (B, C, D, S, P, L, channels_last, w.shape, w.dtype, bias is not None, pos is not None,
                     pos.shape if pos is not None else None)
         return y
@@ -278,12 +311,20 @@ class _PatchEmbed(torch.autograd.Function):
         dy = dy.contiguous()
         if dy.dtype not in _lib.DTYPE:
             dy = dy.float()
-        dw = torch.zeros(wshape, device=x.device, dtype=torch.float32)
-        db = torch.zeros(D, device=x.device, dtype=torch.float32) if has_b else None
+        new = torch.empty if ctx.det else torch.zeros   # the deterministic entry point writes dw / db
+        dw = new(wshape, device=x.device, dtype=torch.float32)
+        db = new(D, device=x.device, dtype=torch.float32) if has_b else None
         dpos = torch.empty(pshape, device=x.device, dtype=torch.float32) if has_p else None
-        _lib.call("lci_patch_embed_bwd", x.data_ptr(), _lib.DTYPE[x.dtype], dy.data_ptr(), _lib.DTYPE[dy.dtype],
-                  dw.data_ptr(), _lib.ptr(db), _lib.ptr(dpos), B, C, D, len(S), _lib.c_array(ctypes.c_int, S, 3, 1),
-                  _lib.c_array(ctypes.c_int, P, 3, 1), int(cl), _lib.stream_of(x))
+        Sa, Pa = _lib.c_array(ctypes.c_int, S, 3, 1), _lib.c_array(ctypes.c_int, P, 3, 1)
+        if ctx.det:
+            ws = _ws(_lib.load().lci_patch_embed_bwd_det_ws_bytes(B, C, D, len(S), Sa, Pa), x.device)
+            _lib.call("lci_patch_embed_bwd_det", x.data_ptr(), _lib.DTYPE[x.dtype], dy.data_ptr(),
+                      _lib.DTYPE[dy.dtype], dw.data_ptr(), _lib.ptr(db), _lib.ptr(dpos), ws.data_ptr(), B, C, D,
+                      len(S), Sa, Pa, int(cl), _lib.stream_of(x))
+        else:
+            _lib.call("lci_patch_embed_bwd", x.data_ptr(), _lib.DTYPE[x.dtype], dy.data_ptr(), _lib.DTYPE[dy.dtype],
+                      dw.data_ptr(), _lib.ptr(db), _lib.ptr(dpos), B, C, D, len(S), Sa, Pa, int(cl),
+                      _lib.stream_of(x))
         if ctx.needs_input_grad[0]:
             raise NotImplementedError("patch_embed: gradient w.r.t. the input image is not provided")
         return None, dw.to(wdtype), (db if has_b else None), dpos, None, None
@@ -422,6 +463,7 @@ class _SelectiveScanCL(torch.autograd.Function):
         if need_grad:
             ctx.save_for_backward(u, delta, Af, Bm, Cm, Dv, bv, sdt, ckpt)
         ctx.tc, ctx.softplus = tc, softplus
+        ctx.det = deterministic()
         ctx.z_half_only = getattr(yz, "_lci_z_half_only", False)
         ctx.has_D, ctx.has_b = D is not None, delta_bias is not None
         if one:   # no final state requested (an empty placeholder output)
@@ -445,21 +487,27 @@ class _SelectiveScanCL(torch.autograd.Function):
         f32 = dict(device=u.device, dtype=torch.float32)
         du = torch.empty_like(u)
         dd = torch.empty(B, L, Dx, device=u.device, dtype=u.dtype)
-        plain = _lib.load().lci_selective_scan_bwd_plain_dbc(L, Dx, tc)   # every entry stored once: no zero fill
+        # every entry stored once: no zero fill (the deterministic entry point: every output, at every shape)
+        plain = ctx.det or _lib.load().lci_selective_scan_bwd_plain_dbc(L, Dx, tc)
         dBC = (torch.empty if plain else torch.zeros)(B, L, 2 * N, **f32)
-        dA = torch.zeros(Dx, N, **f32)
-        dD = torch.zeros(Dx, **f32)
-        db = torch.zeros(Dx, **f32)
+        new = torch.empty if ctx.det else torch.zeros
+        dA = new(Dx, N, **f32)
+        dD = new(Dx, **f32)
+        db = new(Dx, **f32)
         gl = torch.empty(B, nch, Dx, N, **f32)
         gin = torch.empty(B, nch, Dx, N, **f32)
         strides = _lib.c_array(ctypes.c_longlong,
                                [*_bt(u), *_bt(delta), *_bt(Bm), *_bt(Cm), 0, 0, *_bt(dy), *_bt(du), *_bt(dd)])
         es = u.element_size()   # read u, delta, dy, B, C; write du, ddelta, dB, dC
+        args = (_lib.DTYPE[u.dtype], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
+                Cm.data_ptr(), Dv.data_ptr(), bv.data_ptr(), dy.data_ptr(), du.data_ptr(), dd.data_ptr(),
+                dBC.data_ptr(), dA.data_ptr(), dD.data_ptr(), db.data_ptr(), strides, B, L, Dx, N, tc,
+                int(ctx.softplus), _lib.ptr(sdt), ckpt.data_ptr(), gl.data_ptr(), gin.data_ptr())
+        if ctx.det:
+            ws = _ws(_lib.load().lci_selective_scan_bwd_det_ws_bytes(B, L, Dx, tc), u.device)
+            args = (*args, ws.data_ptr())
         KernelTimer.run("selective_scan_bwd", float(B * L * (5 * Dx + 4 * N) * es), u, lambda: _lib.call(
-            "lci_selective_scan_bwd", _lib.DTYPE[u.dtype], u.data_ptr(), delta.data_ptr(), Af.data_ptr(), Bm.data_ptr(),
-            Cm.data_ptr(), Dv.data_ptr(), bv.data_ptr(), dy.data_ptr(), du.data_ptr(), dd.data_ptr(),
-            dBC.data_ptr(), dA.data_ptr(), dD.data_ptr(), db.data_ptr(), strides, B, L, Dx, N, tc,
-            int(ctx.softplus), _lib.ptr(sdt), ckpt.data_ptr(), gl.data_ptr(), gin.data_ptr(), _lib.stream_of(u)))
+            "lci_selective_scan_bwd_det" if ctx.det else "lci_selective_scan_bwd", *args, _lib.stream_of(u)))
         # grad of yz: its first half was overwritten by y (zero gradient there), its second half is the SiLU(conv z)
         # operand of the out_proj input. When yz came from dwconv_silu_pair (tagged there), whose backward reads
         # only the z half (column offset C), gyz passes through as is instead of a clone + zero of the x half (a
@@ -889,6 +937,7 @@ class _FFTConv(torch.autograd.Function):
         del S
         ctx.save_for_backward(u, K, Su)
         ctx.kdtype = k.dtype
+        ctx.det = deterministic()
         return y
 
     @staticmethod
@@ -902,15 +951,19 @@ class _FFTConv(torch.autograd.Function):
         want_k = ctx.needs_input_grad[1]
         want_d = ctx.needs_input_grad[2]
         dk = torch.empty(C, L, device=u.device, dtype=torch.float32) if want_k else None
-        dD = torch.zeros(C, device=u.device, dtype=torch.float32) if want_d else None
+        # (the deterministic entry point writes dD)
+        dD = (torch.empty if ctx.det else torch.zeros)(C, device=u.device, dtype=torch.float32) if want_d else None
         P = (R + 1) // 2
         S = torch.empty(C * P, n, 2, device=u.device, dtype=torch.float32)
         S2 = torch.empty(C * P, n, 2, device=u.device, dtype=torch.float32) if (want_k and Su is None) else None
         SK = torch.empty(C, n, 2, device=u.device, dtype=torch.float32) if want_k else None
+        args = (dy.data_ptr(), u.data_ptr(), K.data_ptr(), None, du.data_ptr(), _lib.ptr(dk), _lib.ptr(dD),
+                S.data_ptr(), _lib.ptr(S2), _lib.ptr(Su if want_k else None), _lib.ptr(SK), tw.data_ptr())
+        if ctx.det:   # per-(row, split) dot products for a dD without dk
+            ws = _ws(_lib.load().lci_fftconv_bwd_det_ws_bytes(R, C, L), u.device) if want_d and not want_k else None
+            args = (*args, _lib.ptr(ws))
         KernelTimer.run("fftconv_bwd", float(R * C * L), u, lambda: _lib.call(
-            "lci_fftconv_bwd", dy.data_ptr(), u.data_ptr(), K.data_ptr(), None, du.data_ptr(),
-            _lib.ptr(dk), _lib.ptr(dD), S.data_ptr(), _lib.ptr(S2), _lib.ptr(Su if want_k else None), _lib.ptr(SK),
-            tw.data_ptr(), R, C, L, _lib.stream_of(u)))
+            "lci_fftconv_bwd_det" if ctx.det else "lci_fftconv_bwd", *args, R, C, L, _lib.stream_of(u)))
         return du, (dk.to(ctx.kdtype) if dk is not None else None), dD
 
 
@@ -1004,6 +1057,7 @@ class _HyenaPre(torch.autograd.Function):
             x2.data_ptr(), BB, L, num_heads, hd, K, _lib.stream_of(z)))
         ctx.save_for_backward(z, wf, bf)
         ctx.meta = (num_heads, w.shape, b is not None)
+        ctx.det = deterministic()
         return vg, x2
 
     @staticmethod
@@ -1020,11 +1074,17 @@ class _HyenaPre(torch.autograd.Function):
         dx2 = (torch.zeros(BB, L, D, device=z.device, dtype=z.dtype) if dx2 is None
                else dx2.to(z.dtype).contiguous())
         dz = torch.empty_like(z)
-        dw = torch.zeros(C3, K, **f32)
-        db = torch.zeros(C3, **f32) if has_b else None
+        new = torch.empty if ctx.det else torch.zeros   # the deterministic entry point writes dw / db
+        dw = new(C3, K, **f32)
+        db = new(C3, **f32) if has_b else None
+        args = (_lib.DTYPE[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), dvg.data_ptr(), dx2.data_ptr(),
+                dz.data_ptr(), dw.data_ptr(), _lib.ptr(db))
+        if ctx.det:
+            ws = _ws(_lib.load().lci_hyena_pre_bwd_det_ws_bytes(BB, L, num_heads, hd, K), z.device)
+            args = (*args, ws.data_ptr())
         KernelTimer.run("hyena_pre_bwd", 0.0, z, lambda: _lib.call(
-            "lci_hyena_pre_bwd", _lib.DTYPE[z.dtype], z.data_ptr(), wf.data_ptr(), _lib.ptr(bf), dvg.data_ptr(),
-            dx2.data_ptr(), dz.data_ptr(), dw.data_ptr(), _lib.ptr(db), BB, L, num_heads, hd, K, _lib.stream_of(z)))
+            "lci_hyena_pre_bwd_det" if ctx.det else "lci_hyena_pre_bwd", *args, BB, L, num_heads, hd, K,
+            _lib.stream_of(z)))
         return dz, dw.reshape(wshape), db, None
 
 

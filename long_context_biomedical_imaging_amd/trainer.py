@@ -269,6 +269,9 @@ class TrainStep:
         self.hold_sched = False   # GraphedStep: the captured step must not advance the host mirror
         self.loss_func = loss_fn(config)
         self.use_amp = bool(config.use_amp)
+        # --deterministic: every step runs under kernels.deterministic_mode (fixed-order gradient sums);
+        # a GraphedStep of this trainer captures those launches
+        self.deterministic = bool(getattr(config, "deterministic", False))
         self.clip = float(getattr(config, "clip_grad_norm", 0.0) or 0.0)
         # the clip on a CUDA LciAdam(W): norm and coefficient by kernels.grad_clip_coef, the multiply inside the
         # update kernel (p.grad itself stays unscaled; it is zeroed right after the step)
@@ -288,6 +291,13 @@ class TrainStep:
         of an accumulation window, i.e. every `iters_to_accumulate` calls (`update=None`), as the reference's
         `(idx + 1) % iters_to_accumulate == 0`. `update=True` forces the step (the reference's last iteration of an
         epoch, `idx + 1 == total_iters`), `update=False` suppresses it."""
+        if self.deterministic:
+            from . import kernels
+            with kernels.deterministic_mode(True):
+                return self._step(inputs, targets, update)
+        return self._step(inputs, targets, update)
+
+    def _step(self, inputs, targets, update):
         if inputs.shape[0] == 1 and self.dup_batch1:
             inputs = torch.cat([inputs] * 2, dim=0)
             targets = torch.cat([targets] * 2, dim=0)
