@@ -345,7 +345,10 @@ int lci_mamba_proj_bwd(const void* ddt, long long ts_ddt, const void* dbc, const
 
 /* ------------------------------------------------------------------ Hyena long convolution (f32)
  * FFT size n = lci_fft_size(L) = pow2 >= 2L (L <= 262144). tw: n complex f32 (f32x2) from lci_fft_twiddles.
- * Rows are channel-major f32 (R, C, L); the filter of row r is r % C; k (C, L). */
+ * Rows are channel-major f32 (R, C, L); the filter of row r is r % C; k (C, L).
+ * Alignment (checked, rc 1): every complex workspace (K, SK, S, S2, Su, tw) is 16-byte aligned; the row tensors
+ * (k, u, y, dy, du) are 16-byte aligned when L % 4 == 0 (their rows are then accessed as 16-byte vectors) and need
+ * only the 4 bytes of a float at any other L. */
 long long lci_fft_size(int L);
 int lci_fft_twiddles(void* tw, int n, void* stream);
 /* K (C, n) complex f32 = filter spectra (scaled by 1/n); SK (C, n) complex scratch. Dv (C) or null: folded into the

@@ -1622,6 +1622,19 @@ extern "C" int lci_fft_twiddles(void* tw, int n, void* stream) {
   return 0;
 }
 
+// Alignment preconditions of the long conv (lci.h): every complex workspace is read and written as 16-byte vectors,
+// and so are the f32 rows when L % 4 == 0 (the scalar row accesses of other L need only the 4 bytes of a float).
+static int fft_check_align(const char* who, int L, std::initializer_list<const void*> ws,
+                           std::initializer_list<const void*> rows) {
+  for (const void* p : ws)
+    LCI_CHECK(((uintptr_t)p & 15) == 0, "%s: complex workspace %p is not 16-byte aligned", who, p);
+  if (L % 4 == 0)
+    for (const void* p : rows)
+      LCI_CHECK(((uintptr_t)p & 15) == 0, "%s: row pointer %p is not 16-byte aligned (required when L %% 4 == 0)",
+                who, p);
+  return 0;
+}
+
 static int launch_col(FftArgs& a, bool inv, int nblk_y, hipStream_t s) {
   // wide column kernels: complex elements per workgroup 4096 at n1 <= 512 (~130 instead of ~245 VGPRs, 4 workgroups
   // per CU; >= 8 columns = 32-B row segments), 16384 at n1 = 1024 (16 columns, 64-B row segments, 512 threads, the
@@ -1691,6 +1704,7 @@ extern "C" int lci_fftconv_spectrum(const float* k, const float* Dv, void* K, vo
                                     void* stream) {
   FftArgs a{};
   if (fft_plan(a, L)) return 1;
+  if (fft_check_align("fftconv_spectrum", L, {K, SK, tw}, {k})) return 1;
   a.src = k; a.Dv = Dv; a.K = (f32x2*)K; a.SK = (f32x2*)SK; a.tw = (const f32x2*)tw; a.C = C; a.single = 1; a.mode = 0;
   hipStream_t s = (hipStream_t)stream;
   a.pid0 = 0;
@@ -1706,6 +1720,7 @@ extern "C" int lci_fftconv_fwd(const float* u, const void* K, const float* Dv, f
                                const void* tw, int R, int C, int L, void* stream) {
   FftArgs a{};
   if (fft_plan(a, L)) return 1;
+  if (fft_check_align("fftconv_fwd", L, {K, S, Su, tw}, {u, y})) return 1;
   a.src = u; a.dst = y; a.K = (f32x2*)K; a.tw = (const f32x2*)tw; a.Dv = Dv;
   a.R = R; a.C = C; a.P = (R + 1) / 2; a.single = 0; a.mode = 1;
   hipStream_t s = (hipStream_t)stream;
@@ -1728,6 +1743,7 @@ extern "C" int lci_fftconv_bwd(const float* dy, const float* u, const void* K, c
                                int L, void* stream) {
   FftArgs a{};
   if (fft_plan(a, L)) return 1;
+  if (fft_check_align("fftconv_bwd", L, {K, S, S2, Su, SK, tw}, {dy, u, du})) return 1;
   a.tw = (const f32x2*)tw; a.K = (f32x2*)K; a.S = (f32x2*)S; a.S2 = (f32x2*)(Su ? Su : S2);
   a.SK = dk ? (f32x2*)SK : nullptr;
   a.R = R; a.C = C; a.P = (R + 1) / 2; a.Dv = Dv; a.dk = dk;
@@ -1923,11 +1939,12 @@ extern "C" long long lci_fftconv_bwd_det_ws_bytes(int R, int C, int L) {
 extern "C" int lci_fftconv_bwd_det(const float* dy, const float* u, const void* K, const float* Dv, float* du,
                                    float* dk, float* dD, void* S, void* S2, const void* Su, void* SK, const void* tw,
                                    float* dd_ws, int R, int C, int L, void* stream) {
+  // (checked before anything is launched: a refused call leaves every output as it was)
+  LCI_CHECK(!dD || dk || dd_ws, "fftconv_bwd_det: dD without dk needs dd_ws");
   if (int rc = lci_fftconv_bwd(dy, u, K, Dv, du, dk, nullptr, S, S2, Su, SK, tw, R, C, L, stream)) return rc;
   if (!dD) return 0;
   hipStream_t s = (hipStream_t)stream;
   if (dk) return ordered_sum(dk, 0, L, 1, C, dD, s) ? 3 : 0;
-  LCI_CHECK(dd_ws, "fftconv_bwd_det: dD without dk needs dd_ws");
   const int vec = (L % 4 == 0) && ((uintptr_t)dy & 15) == 0 && ((uintptr_t)u & 15) == 0;
   const int splits = (L + RD_SPAN - 1) / RD_SPAN;
   hipLaunchKernelGGL(row_dot_kernel<true>, dim3(R * C, splits), dim3(256), 0, s, dy, u, dd_ws, L, C, vec);

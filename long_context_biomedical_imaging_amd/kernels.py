@@ -899,9 +899,16 @@ def _fft_n(L):
     return int(_lib.load().lci_fft_size(int(L)))
 
 
+def _aligned16(t):
+    """t, or a copy of it when its first element is not 16-byte aligned (a contiguous view at a storage offset): the
+    long conv reads and writes rows with L % 4 == 0 as 16-byte vectors, and liblci refuses other pointers there."""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _spectrum(k, Dv=None):
     """Filter spectra K = FFT_n(k) / n (+ D / n: the + D u term of fftconv_ref folded into the convolution)."""
     C, L = k.shape
+    k = _aligned16(k)
     n = _fft_n(L)
     tw = _twiddles(n, k.device)
     K = torch.empty(C, n, 2, device=k.device, dtype=torch.float32)
@@ -922,6 +929,7 @@ class _FFTConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, k, D):
         R, C, L = u.shape
+        u = _aligned16(u)
         kf = k.float().contiguous()
         Dv = D.float().contiguous()
         K = _spectrum(kf, Dv)
@@ -946,7 +954,7 @@ class _FFTConv(torch.autograd.Function):
         R, C, L = u.shape
         n = K.shape[1]
         tw = _twiddles(n, u.device)
-        dy = dy.float().contiguous()
+        dy = _aligned16(dy.float().contiguous())
         du = torch.empty_like(u)
         want_k = ctx.needs_input_grad[1]
         want_d = ctx.needs_input_grad[2]
