@@ -17,7 +17,9 @@
  *   lci_attn_*            SABlock.forward attention core, model/models/backbone_vit.py:191-203
  *   lci_window_attn_*     WindowAttention.forward, model/models/backbone_swin.py:339-359, and in grid mode the
  *                         pad/roll/window_partition/window_reverse/crop of SwinTransformerBlock.forward_part1
- *                         (:435-487) with compute_mask (:591-628)
+ *                         (:435-487) with compute_mask (:591-628); windows of at most 768 tokens
+ *   lci_window_long_*     the same in grid mode for windows of up to 4096 tokens, with the gather
+ *                         relative_position_bias_table[relative_position_index[:n, :n]] (:343-346) evaluated per pair
  *   lci_selective_scan_*  mamba_ssm selective_scan_fn (mamba-ssm 1.2.0.post1) as called at model/models/mamba.py:125-134
  *   lci_dwconv_silu_*     MambaVisionMixer depthwise conv1d + SiLU, model/models/mamba.py:118-119
  *   lci_mamba_proj_*      MambaVisionMixer x_proj -> (dt, B, C) split -> dt_proj, model/models/mamba.py:120-124
@@ -81,8 +83,8 @@ extern "C" {
  * 38: lci_adam_step_ex, lci_onecycle_eval, lci_grad_sumsq (+ _parts), lci_grad_clip_coef; 39: lci_class_*;
  * 40: lci_augment (+ _ws_bytes); 41: lci_attn_bwd_variant2, lci_attn_bwd_dkdv_pick; 42: the deterministic mode:
  * lci_ordered_sum, lci_selective_scan_bwd_det, lci_hyena_pre_bwd_det, lci_fftconv_bwd_det, lci_patch_embed_bwd_det
- * (+ _ws_bytes each). */
-#define LCI_ABI_VERSION 42
+ * (+ _ws_bytes each); 43: lci_window_long_* (windows of up to 4096 tokens). */
+#define LCI_ABI_VERSION 43
 const char* lci_last_error(void);
 int lci_abi_version(void);
 /* sha256 prefix of the sources the library was built from (build_lib.source_hash); the Python binding refuses a
@@ -209,6 +211,35 @@ int lci_window_index_map(const int* geo, int* src_row, int* region, int* rid, in
  * elem_bytes (2 or 4) bytes, C * elem_bytes % 16 == 0, 16-byte aligned; geo as above (mode 1, C in geo[14]). The
  * index map is win_row(), the one the attention kernels and lci_window_index_map use. */
 int lci_window_gather(const void* src, void* dst, int elem_bytes, const int* geo, int scatter, void* stream);
+
+/* ------------------------------------------------------------------ Swin window attention, large windows
+ * Grid mode only (geo[0] == 1), head_dim 32, N <= 4096 tokens per window (any N >= 1 is accepted; the models send
+ * N > 768 here). Streaming kernels (csrc/window_long.hip): no N^2-sized table; the additive logit term
+ *   table[rel(q, k)][h] (+ -100 across compute_mask regions)
+ * is evaluated in the kernel from the module's parameter `table` (n_tab, H) f32, n_tab = prod_s (2 full[s] - 1)
+ * <= 29791. full[nd] = the module's full window; geo's ws is the window get_window_size chose for the grid
+ * (ws[s] <= full[s]). Token j of a clamped window is raster position j of the full one (relative_position_index
+ * [:n, :n]): rel(q, k) = sum_s (c_q[s] - c_k[s] + full[s] - 1) * prod_{t>s} (2 full[t] - 1), c = the coordinates of
+ * the raster position in the full window. Padded voxels take q/k/v = qkv_bias (f32, 3C, may be null = zeros).
+ * out (B, S.., C) bf16, lse2 (Bw, H, N) f32 (log2 domain). Deterministic: no float atomics on any path. */
+int lci_window_long_fwd(const void* qkv, const float* qkv_bias, const float* table, void* out, float* lse2,
+                        const int* geo, const int* full, float scale, void* stream);
+/* dqkv (layout of qkv) <- dQ/dK/dV, every element written; delta (Bw, H, N) f32 scratch (written, then read);
+ * dbias_pad (3C f32, may be null) <- the qkv-bias gradient through the padded voxels (q third zero), written, with
+ * pad_ws an f32 workspace of lci_window_long_pad_ws_elems elements; dtable (n_tab, H) f32 (may be null) <- the
+ * table gradient, written, with ws a 256-byte aligned workspace of lci_window_long_ws_bytes bytes: the bf16 dS of
+ * lci_window_long_ws_items (window, head) items per pass (an item = N x ceil(N/32)*32 bf16) plus at most
+ * (32, n_tab, H) f32 partials -- bounded by LCI_WIN_LONG_WS_MB (default 256, read once per process; at least one
+ * item), independent of the number of windows. The launch list is fixed by geo, full and that budget (capturable);
+ * the result does not depend on the budget. */
+int lci_window_long_bwd(const void* qkv, const float* qkv_bias, const float* table, const void* out, const void* dout,
+                        const float* lse2, void* dqkv, float* delta, float* dbias_pad, float* pad_ws, float* dtable,
+                        void* ws, const int* geo, const int* full, float scale, void* stream);
+long long lci_window_long_pad_ws_elems(const int* geo, const int* full);
+long long lci_window_long_ws_bytes(const int* geo, const int* full);
+long long lci_window_long_ws_items(const int* geo, const int* full);
+/* idx (N, N) int32 = rel(q, k) as the kernels evaluate it (test/inspection entry). */
+int lci_window_long_index(const int* geo, const int* full, int* idx, void* stream);
 
 /* ------------------------------------------------------------------ decoder-head 3x3(x3) convolution
  * Replaces the kernel-3 stride-1 convs of MONAI-1.3 UnetResBlock (get_conv_layer conv_only, bias=False) in the

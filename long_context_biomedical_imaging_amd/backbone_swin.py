@@ -151,6 +151,16 @@ class WindowAttention(nn.Module):
                                  f"(DESIGN.md §7)")
             self.scale = head_dim ** -0.5
             n_tab = int(np.prod([2 * w - 1 for w in window_size]))
+            n_tok = int(np.prod(list(window_size)))
+            if n_tok > kernels.WIN_LONG_MAX_TOKENS or (n_tok > kernels.WIN_MAX_TOKENS
+                                                       and n_tab > kernels.WIN_LONG_MAX_TABLE):
+                # csrc/window_long.hip streams windows of 769 .. 4096 tokens whose table has <= 29791 rows; beyond
+                # that no kernel exists: fail here, not in the middle of the first forward
+                raise ValueError(f"window attention window_size {tuple(window_size)} ({n_tok} tokens, a relative-"
+                                 f"position table of {n_tab} rows) is not supported: the HIP window kernels take at "
+                                 f"most {kernels.WIN_LONG_MAX_TOKENS} tokens per window and, above "
+                                 f"{kernels.WIN_MAX_TOKENS} tokens, a table of at most {kernels.WIN_LONG_MAX_TABLE} "
+                                 f"rows (DESIGN.md §7)")
             self.relative_position_bias_table = nn.Parameter(torch.zeros(n_tab, num_heads))
             self.register_buffer("relative_position_index", relative_position_index(window_size))
             self.qkv = TokenLinear(dim, dim * 3, bias=qkv_bias)
@@ -196,6 +206,12 @@ class WindowAttention(nn.Module):
         n = int(np.prod(window_size))
         qkv = self.qkv(xn)
         bias = self.qkv.bias
+        if n > kernels.WIN_MAX_TOKENS:
+            # large windows: the streaming kernels evaluate table[index[:n, :n]] per pair from the table itself
+            o = kernels.window_attention_grid_long(qkv, bias, self.relative_position_bias_table, self.num_heads,
+                                                   self.scale, tuple(window_size), tuple(shift_size),
+                                                   tuple(self.window_size))
+            return self.proj_drop(self.proj(o))
         o = kernels.window_attention_grid(qkv, bias, self.rel_bias(n), self.num_heads, self.scale,
                                           tuple(window_size), tuple(shift_size))
         return self.proj_drop(self.proj(o))

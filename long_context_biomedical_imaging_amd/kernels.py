@@ -186,6 +186,9 @@ class _FlashAttention(torch.autograd.Function):
 ATTN_HEAD_DIM = 64        # csrc/attention.hip DH (the placed bf16 kernels)
 ATTN_GEN_MAX_HEAD_DIM = 256   # csrc/attention_gen.hip (f32 products: fp32 mode, and head dims above 64)
 WIN_HEAD_DIM = 32    # csrc/window.hip WHD
+WIN_MAX_TOKENS = 768          # csrc/window_geo.hpp WMAXN: windows the resident kernels (csrc/window.hip) take
+WIN_LONG_MAX_TOKENS = 4096    # csrc/window_long.hip WL_MAXN: the streaming large-window kernels (grid mode)
+WIN_LONG_MAX_TABLE = 29791    # csrc/window_long.hip WL_MAXTAB: rows of their relative-position table (16^3 window)
 
 
 def attn_gen_fwd(qkv: torch.Tensor, num_heads: int, scale: float):
@@ -802,6 +805,84 @@ def window_attention_grid(qkv, bias, rpb, num_heads, scale, window_size, shift_s
     return o if dt == torch.bfloat16 else o.to(dt)
 
 
+class _WindowAttentionLong(torch.autograd.Function):
+    """csrc/window_long.hip: streaming window attention on the grid, the logit term evaluated from the table."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, table, geo, full, scale):
+        C = qkv.shape[-1] // 3
+        out = torch.empty(*qkv.shape[:-1], C, device=qkv.device, dtype=torch.bfloat16)
+        g, fw = _i32(geo), _i32(full)
+        N, H = geo[13], geo[15]
+        Bw = geo[11] * geo[12]
+        lse2 = torch.empty(Bw, H, N, device=qkv.device, dtype=torch.float32)
+        bf = bias.float().contiguous() if bias is not None else None
+        tb = table.float().contiguous()
+        KernelTimer.run("window_long_fwd", 4.0 * Bw * H * N * N * 32, qkv, lambda: _lib.call(
+            "lci_window_long_fwd", qkv.data_ptr(), _lib.ptr(bf), tb.data_ptr(), out.data_ptr(), lse2.data_ptr(),
+            g, fw, float(scale), _lib.stream_of(qkv)))
+        ctx.save_for_backward(qkv, bf, tb, out, lse2)
+        ctx.geo, ctx.full, ctx.scale, ctx.has_bias = geo, full, scale, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, bf, tb, out, lse2 = ctx.saved_tensors
+        geo, full, scale = ctx.geo, ctx.full, ctx.scale
+        g, fw = _i32(geo), _i32(full)
+        N, C, H = geo[13], geo[14], geo[15]
+        Bw = lse2.shape[0]
+        lib = _lib.load()
+        dout = dout.to(torch.bfloat16).contiguous()
+        dqkv = torch.empty_like(qkv)
+        f32 = dict(device=qkv.device, dtype=torch.float32)
+        delta = torch.empty_like(lse2)
+        dbias = pad_ws = dtable = ws = None
+        if ctx.has_bias and ctx.needs_input_grad[1]:
+            dbias = torch.empty(3 * C, **f32)
+            pad_ws = torch.empty(int(lib.lci_window_long_pad_ws_elems(g, fw)), **f32)
+        if ctx.needs_input_grad[2]:
+            dtable = torch.empty_like(tb)
+            ws = torch.empty(int(lib.lci_window_long_ws_bytes(g, fw)), device=qkv.device, dtype=torch.uint8)
+        KernelTimer.run("window_long_bwd", 8.0 * Bw * H * N * N * 32, qkv, lambda: _lib.call(
+            "lci_window_long_bwd", qkv.data_ptr(), _lib.ptr(bf), tb.data_ptr(), out.data_ptr(), dout.data_ptr(),
+            lse2.data_ptr(), dqkv.data_ptr(), delta.data_ptr(), _lib.ptr(dbias), _lib.ptr(pad_ws), _lib.ptr(dtable),
+            _lib.ptr(ws), g, fw, float(scale), _lib.stream_of(qkv)))
+        return dqkv, dbias, dtable, None, None, None
+
+
+def window_long_index(window_size, full_window, device="cuda"):
+    """rel(q, k) as the large-window kernels evaluate it (lci_window_long_index): int32 (N, N) for a window of
+    `window_size` (N = its product) of a module whose full window is `full_window`."""
+    geo = grid_geo(1, list(window_size), window_size, [0] * len(window_size), 32, 1)
+    N = geo[13]
+    idx = torch.empty(N, N, device=device, dtype=torch.int32)
+    _lib.call("lci_window_long_index", _i32(geo), _i32(full_window), idx.data_ptr(),
+              torch.cuda.current_stream(torch.device(device)).cuda_stream)
+    return idx
+
+
+def window_attention_grid_long(qkv, bias, table, num_heads, scale, window_size, shift_size, full_window):
+    """window_attention_grid for windows of up to WIN_LONG_MAX_TOKENS tokens (csrc/window_long.hip).
+
+    qkv, bias as window_attention_grid; table: the module's (n_tab, H) relative_position_bias_table itself, n_tab =
+    prod(2 w - 1) over `full_window` (the module's window; `window_size` is the one get_window_size chose for this
+    grid). The kernels evaluate table[index[:n, :n]] and the -100 region mask per pair; the gradient comes back on
+    the table. Deterministic in every mode."""
+    _lib.require_gpu(qkv.contiguous())
+    q, dt = _win_prep(qkv)
+    hd = q.shape[-1] // (3 * num_heads)
+    _check_head_dim(hd, WIN_HEAD_DIM, "window attention")
+    if hd < WIN_HEAD_DIM:
+        q = pad_heads(q, 3, num_heads, WIN_HEAD_DIM).contiguous()
+        bias = None if bias is None else pad_heads(bias, 3, num_heads, WIN_HEAD_DIM)
+    geo = grid_geo(q.shape[0], q.shape[1:-1], window_size, shift_size, q.shape[-1] // 3, num_heads)
+    o = _WindowAttentionLong.apply(q, bias, table, geo, tuple(int(w) for w in full_window), scale)
+    if hd < WIN_HEAD_DIM:
+        o = unpad_heads(o, num_heads, hd)
+    return o if dt == torch.bfloat16 else o.to(dt)
+
+
 def _win_move(src, dst, geo, scatter):
     _lib.call("lci_window_gather", src.data_ptr(), dst.data_ptr(), src.element_size(), _i32(geo),
               int(scatter), _lib.stream_of(src))
@@ -865,6 +946,10 @@ def window_reverse_grid(win, grid_shape, window_size, shift_size):
 
 def window_attention(qkv, rpb, mask, num_heads, scale):
     """Pre-partitioned windows (WindowAttention.forward signature): qkv (Bw, N, 3C), mask (nW, N, N) or None."""
+    if qkv.shape[1] > WIN_MAX_TOKENS:
+        raise _lib.LciError(f"window_attention: N {qkv.shape[1]} unsupported (<= {WIN_MAX_TOKENS}) for pre-partitioned "
+                            f"windows; windows of up to {WIN_LONG_MAX_TOKENS} tokens run on the grid path "
+                            "(WindowAttention.forward_grid / kernels.window_attention_grid_long)")
     _lib.require_gpu(qkv.contiguous())
     q, dt = _win_prep(qkv)
     hd = q.shape[-1] // (3 * num_heads)
