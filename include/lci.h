@@ -283,7 +283,9 @@ int lci_conv3_wgrad(const void* x, const void* dy, float* part, int B, int D, in
  * apply: dz null -> out = act ? lrelu(n) : n;  else out = dx = rstd * (dn - coef0 - n * coef1), coef (B, 2, C)
  *   = voxel means of (dn, dn*n).
  * finalize: the partial sums (in f64, fixed order) -> out (B, 2, C): mode 0 the stats (mean, rstd with eps), mode 1
- *   the coefficients (the voxel means of both sums). */
+ *   the coefficients (the voxel means of both sums).
+ * x, dz, out, and the stats and coef that lci_inorm_apply / lci_inorm_apply_res read, are 16-byte aligned (vector
+ * loads); a call with another pointer is refused (rc 1) before anything is launched. */
 int lci_inorm_chunks(long long V, int B);
 int lci_inorm_reduce(const void* x, const void* dz, const float* stats, float* part, long long V, int B, int C,
                      int act, float slope, void* stream);
@@ -293,7 +295,7 @@ int lci_inorm_finalize(const float* part, float* out, long long V, int B, int C,
  * lci_inorm_reduce / lci_inorm_finalize with B = 1. Forward y (V, C) f32 = relu((x - mean) rstd w + b). Backward:
  * part (2, C, lci_inorm_chunks(V, 1)) sums of g = dy [y > 0] and g xhat (dy f32 when dy_f32, else bf16), then
  * lci_inorm_finalize mode 1 -> coef (2, C) means, then dx (V, C) bf16 = (g - coef0 - xhat coef1) rstd w.
- * C % 8 == 0, C <= 2048, 16-byte aligned. */
+ * C % 8 == 0, C <= 2048; x, dy, y, dx, stats, coef, w and b 16-byte aligned (refused otherwise, rc 1). */
 int lci_bn_relu_fwd(const void* x, const float* stats, const float* w, const float* b, float* y, long long V, int C,
                     void* stream);
 int lci_bn_relu_bwd_reduce(const void* x, const void* dy, int dy_f32, const float* stats, const float* w,

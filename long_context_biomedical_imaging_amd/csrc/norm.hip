@@ -250,6 +250,16 @@ __device__ __forceinline__ void load_wb(const float* w, const float* b, int g, f
   for (int j = 0; j < 4; ++j) { wv[j] = w0[j]; wv[4 + j] = w1[j]; bv[j] = b0[j]; bv[4 + j] = b1[j]; }
 }
 
+// xhat * w + b as a rounded product and a rounded sum, torch's two operations. HIP's __fmul_rn / __fadd_rn are plain
+// `*` and `+` (only CUDA's keep the compiler from fusing them), so written with them the pair became one fma: a value
+// one f32 ulp from torch's in about one element of seven. The forward and both backward kernels take the ReLU mask
+// from this one function, so the three agree by construction.
+__device__ __forceinline__ float bn_affine(float xhat, float w, float b) {
+#pragma clang fp contract(off)
+  const float p = xhat * w;
+  return p + b;
+}
+
 __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(BnArgs a) {
   const int G = a.C >> 3;
   const long long e = blockIdx.x * 256LL + threadIdx.x;
@@ -263,7 +273,7 @@ __global__ __launch_bounds__(256) void bn_relu_fwd_kernel(BnArgs a) {
   float o[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(x[j], mu[j]), rs[j]), wv[j]), bv[j]);
+    const float v = bn_affine(__fmul_rn(__fsub_rn(x[j], mu[j]), rs[j]), wv[j], bv[j]);
     o[j] = v > 0.f ? v : 0.f;
   }
   *(f32x4*)y = f32x4{o[0], o[1], o[2], o[3]};
@@ -291,7 +301,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(BnArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float n = __fmul_rn(__fsub_rn(x[j], mu[j]), rs[j]);
-        const float gg = __fadd_rn(__fmul_rn(n, w[j]), bb[j]) > 0.f ? d[j] : 0.f;
+        const float gg = bn_affine(n, w[j], bb[j]) > 0.f ? d[j] : 0.f;
         s1[j] += gg;
         s2[j] += gg * n;
       }
@@ -329,7 +339,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(BnArgs a) {
   for (int j = 0; j < 8; ++j) {
     const float w = wv[j];
     const float n = __fmul_rn(__fsub_rn(x[j], mu[j]), rs[j]);
-    const float gg = __fadd_rn(__fmul_rn(n, w), bv[j]) > 0.f ? d[j] : 0.f;
+    const float gg = bn_affine(n, w, bv[j]) > 0.f ? d[j] : 0.f;
     o[j] = to_bf16((gg - m1[j] - n * m2[j]) * (rs[j] * w));
   }
   *(bf16x8*)((bf16*)a.out + e * 8) = o;
@@ -346,7 +356,8 @@ extern "C" int lci_inorm_chunks(long long V, int B);
 extern "C" int lci_bn_relu_fwd(const void* x, const float* stats, const float* w, const float* b, float* y,
                                long long V, int C, void* stream) {
   LCI_CHECK(V > 0 && C > 0 && C % 8 == 0 && C <= 2048, "bn_relu: bad shape");
-  LCI_CHECK((((uintptr_t)x | (uintptr_t)y | (uintptr_t)stats) & 15) == 0, "bn_relu: misaligned buffers");
+  LCI_CHECK((((uintptr_t)x | (uintptr_t)y | (uintptr_t)stats | (uintptr_t)w | (uintptr_t)b) & 15) == 0,
+            "bn_relu: misaligned buffers");
   BnArgs a = {};
   a.x = (const bf16*)x; a.stats = stats; a.w = w; a.b = b; a.out = y; a.V = V; a.C = C;
   const long long groups = V * (C / 8);
@@ -360,7 +371,8 @@ extern "C" int lci_bn_relu_fwd(const void* x, const float* stats, const float* w
 extern "C" int lci_bn_relu_bwd_reduce(const void* x, const void* dy, int dy_f32, const float* stats, const float* w,
                                       const float* b, float* part, long long V, int C, void* stream) {
   LCI_CHECK(V > 0 && C > 0 && C % 8 == 0 && C <= 2048, "bn_relu: bad shape");
-  LCI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)stats) & 15) == 0, "bn_relu: misaligned buffers");
+  LCI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)stats | (uintptr_t)w | (uintptr_t)b) & 15) == 0,
+            "bn_relu: misaligned buffers");
   BnArgs a = {};
   a.x = (const bf16*)x; a.dy = dy; a.dy_f32 = dy_f32; a.stats = stats; a.w = w; a.b = b; a.part = part;
   a.V = V; a.C = C;
@@ -376,8 +388,8 @@ extern "C" int lci_bn_relu_bwd_reduce(const void* x, const void* dy, int dy_f32,
 extern "C" int lci_bn_relu_bwd_apply(const void* x, const void* dy, int dy_f32, const float* stats, const float* coef,
                                      const float* w, const float* b, void* dx, long long V, int C, void* stream) {
   LCI_CHECK(V > 0 && C > 0 && C % 8 == 0 && C <= 2048, "bn_relu: bad shape");
-  LCI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)stats | (uintptr_t)coef) & 15) == 0,
-            "bn_relu: misaligned buffers");
+  LCI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)stats | (uintptr_t)coef | (uintptr_t)w |
+              (uintptr_t)b) & 15) == 0, "bn_relu: misaligned buffers");
   BnArgs a = {};
   a.x = (const bf16*)x; a.dy = dy; a.dy_f32 = dy_f32; a.stats = stats; a.coef = coef; a.w = w; a.b = b; a.out = dx;
   a.V = V; a.C = C;
@@ -415,6 +427,7 @@ static int norm_check(long long V, int B, int C, const void* x) {
 extern "C" int lci_inorm_reduce(const void* x, const void* dz, const float* stats, float* part, long long V, int B,
                                 int C, int act, float slope, void* stream) {
   if (norm_check(V, B, C, x)) return 1;
+  LCI_CHECK(!dz || ((uintptr_t)dz & 15) == 0, "inorm: misaligned buffers");
   NormArgs a = {};
   a.x = (const bf16*)x; a.dz = (const bf16*)dz; a.stats = stats; a.part = part;
   a.V = V; a.C = C; a.act = act; a.slope = slope;
@@ -433,6 +446,7 @@ extern "C" int lci_inorm_apply(const void* x, const void* dz, const float* stats
                                long long V, int B, int C, int act, float slope, void* stream) {
   if (norm_check(V, B, C, x)) return 1;
   LCI_CHECK(((uintptr_t)out & 15) == 0 && (!dz || ((uintptr_t)dz & 15) == 0), "inorm: misaligned buffers");
+  LCI_CHECK(((uintptr_t)stats & 15) == 0 && (!dz || ((uintptr_t)coef & 15) == 0), "inorm: misaligned stats");
   NormArgs a = {};
   a.x = (const bf16*)x; a.dz = (const bf16*)dz; a.stats = stats; a.coef = coef; a.out = (bf16*)out;
   a.V = V; a.C = C; a.act = act; a.slope = slope;

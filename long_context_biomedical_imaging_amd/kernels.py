@@ -1888,10 +1888,13 @@ class _BatchNormReLU(torch.autograd.Function):
 
 def batch_norm_relu_supported(x: torch.Tensor, bn) -> bool:
     """The fused training BatchNorm + ReLU takes a bf16 map with dense channels-last strides, 8 | C <= 2048, an
-    affine BN with eps 1e-5 and a momentum, in training mode."""
+    affine BN with eps 1e-5 and a momentum, in training mode, its weight and bias 16-byte aligned (the kernels read
+    them with 16-byte vector loads and lci_bn_relu_* rejects anything else)."""
     C = x.shape[1]
     if not (x.is_cuda and x.dtype == torch.bfloat16 and bn.training and bn.affine and bn.track_running_stats
             and bn.momentum is not None and bn.eps == INORM_EPS and C % 8 == 0 and C <= 2048):
+        return False
+    if bn.weight.data_ptr() % 16 or bn.bias.data_ptr() % 16:
         return False
     x_cl = x.movedim(1, -1)
     return x_cl.is_contiguous() and x_cl.data_ptr() % 16 == 0 and x.numel() // C > 1

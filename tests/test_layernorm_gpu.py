@@ -5,6 +5,18 @@ element is the bf16 rounding of the fp32 result, so it may differ from torch's r
 values straddle a rounding boundary: |err| <= 1 bf16 ulp of the reference + 1e-5 (the f32 absolute error where
 y = n gamma + beta cancels to near zero) everywhere, >= 99.5 % bit-equal.
 Gradients (dx, dgamma, dbeta) vs torch autograd in fp64 on the same cotangent: rel-L2 <= 1e-5.
+
+test_layernorm_stats_and_gradients_per_element calls kernels._ln_fwd / _ln_bwd (the wrappers of lci_layernorm_fwd and
+lci_layernorm_bwd) and checks against plain fp64 expressions, per element:
+  saved mean: |err| <= (4 NV + 6) 2^-24 mean_C|x| = dm (NV = ceil(C / 256): a lane adds 4 NV values, the wave tree six
+  more levels); saved rstd: relative error <= 2^-22 + dvar / (2 (var + eps)), dvar = 2 mean_C|x - m| dm
+  + (4 NV + 9) 2^-24 var (the shifted mean, then the f32 sum of squares with three more roundings per term; 2^-22
+  covers the division, the eps add and the hardware rsqrt)
+  dx: |err| <= 1e-5 max_row|ref| + 1e-7 (rows are independent problems: the row maximum is the natural scale)
+  dgamma, dbeta: |err| <= 1e-5 sum_rows|dy n| and 1e-5 sum_rows|dy| (test_linear_gpu.py's rule for an f32 sum)
+for the plain, residual (dres), tap (dres + dres2) and bf16-branch (dxb) forms; dxb is bitwise bf16(dx). Shapes beyond
+the parity test's: C = 1792 (NV = 7, full), C = 1540 (NV = 7, the last column group partly dead), C = 4 (one live
+lane), rows = 3 (an idle wave contributes zero partials).
 """
 import pytest
 import torch
@@ -16,7 +28,8 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("rows,C", [(1, 384), (4099, 384), (513, 192), (257, 768), (130, 1024), (77, 100),
-                                    (2 * 65536, 384), (97, 1536), (33, 2048), (41, 1030), (19, 2052), (25, 6)])
+                                    (2 * 65536, 384), (97, 1536), (33, 2048), (41, 1030), (19, 2052), (25, 6),
+                                    (29, 1792), (23, 1540), (9, 4), (3, 384)])
 @pytest.mark.parametrize("bf16", [False, True])
 def test_layernorm_vs_torch(rows, C, bf16):
     from long_context_biomedical_imaging_amd import kernels
@@ -45,6 +58,52 @@ def test_layernorm_vs_torch(rows, C, bf16):
     assert rel_err(xc.grad, xr.grad) < 1e-5
     assert rel_err(wc.grad, wr.grad) < 1e-5
     assert rel_err(bc.grad, br.grad) < 1e-5
+
+
+@pytest.mark.parametrize("rows,C", [(29, 1792), (23, 1540), (9, 4), (3, 384), (4099, 384), (97, 1536), (41, 1028),
+                                    (130, 1024)])
+@pytest.mark.parametrize("form", ["plain", "dres", "tap", "dxb"])
+@pytest.mark.parametrize("bf16", [False, True])
+def test_layernorm_stats_and_gradients_per_element(rows, C, form, bf16):
+    from long_context_biomedical_imaging_amd import kernels
+    g = torch.Generator().manual_seed(31 * rows + C)
+    x = torch.randn(rows, C, generator=g) * 3 + 0.5
+    w = 1 + 0.1 * torch.randn(C, generator=g)
+    b = 0.1 * torch.randn(C, generator=g)
+    dy = torch.randn(rows, C, generator=g) + 0.5
+    dy = dy.to(torch.bfloat16) if bf16 else dy
+    dres = torch.randn(rows, C, generator=g) if form != "plain" else None
+    dres2 = torch.randn(rows, C, generator=g) if form in ("tap", "dxb") else None
+    NV = -(-C // 256)
+    # fp64 side
+    xd, dyd = x.double(), dy.double()
+    m = xd.mean(1, keepdim=True)
+    var = ((xd - m) ** 2).mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + 1e-5)
+    n = (xd - m) * rstd
+    gg = dyd * w.double()
+    dx_ref = rstd * (gg - gg.mean(1, keepdim=True) - n * (gg * n).mean(1, keepdim=True))
+    for t in (dres, dres2):
+        if t is not None:
+            dx_ref = dx_ref + t.double()
+    # device side
+    dev = lambda t: None if t is None else t.cuda()  # noqa: E731
+    xc, wc, bc = dev(x), dev(w), dev(b)
+    y, x2, mean, rstd_k = kernels._ln_fwd(xc, wc, bc, 1e-5, bf16)
+    out = kernels._ln_bwd(x2, wc, mean, rstd_k, dev(dy), dev(dres), (rows, C), want_bf16=form == "dxb",
+                          dres2=dev(dres2))
+    dx, dw, db = (t.cpu() for t in out[:3])
+    dm = (4 * NV + 6) * 2.0 ** -24 * xd.abs().mean(1)
+    assert ((mean.cpu().double() - m[:, 0]).abs() <= dm).all()
+    dvar = 2 * (xd - m).abs().mean(1) * dm + (4 * NV + 9) * 2.0 ** -24 * var[:, 0]
+    rho = 2.0 ** -22 + 0.5 * dvar / (var[:, 0] + 1e-5)
+    assert ((rstd_k.cpu().double() - rstd[:, 0]).abs() <= rho * rstd[:, 0]).all()
+    assert torch.isfinite(dx).all()
+    assert ((dx.double() - dx_ref).abs() <= 1e-5 * dx_ref.abs().amax(1, keepdim=True) + 1e-7).all()
+    assert ((dw.double() - (dyd * n).sum(0)).abs() <= 1e-5 * (dyd * n).abs().sum(0)).all()
+    assert ((db.double() - dyd.sum(0)).abs() <= 1e-5 * dyd.abs().sum(0)).all()
+    if form == "dxb":
+        assert torch.equal(out[3].cpu(), dx.to(torch.bfloat16))
 
 
 def test_token_layernorm_module_autocast():
